@@ -1,7 +1,16 @@
 """Train-step rays/s of the instant-ngp hot path on synthetic 800x800 Lego.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(the headline and what the timed region itself yields). --full adds every
+other measurement: the per-launch times and rooflines (eager steps of their
+own), the density-update costs and cadence, the touched-entry counts, the
+test-render speed, the data-parallel path on a one-rank group, the other
+workloads and the CPU baselines (each still switched off by its --no-*
+option). --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (rank 0), for comparing two builds output for output.
 
 One step = sample 4096 rays of a random training pose -> near/far ->
 march_rays_train -> hash-grid encode -> sigma FFMLP -> trunc_exp -> SH ->
@@ -62,9 +71,17 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--num_rays", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the bench measures (per-launch times "
+                         "and rooflines, density update, touched entries, render, dp path, the other "
+                         "workloads, CPU baselines); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, per-ray losses and sample counts, "
+                         "the step's gradient and the updated parameters; the hash table as a fixed seeded "
+                         "sample of its entries) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
     ap.add_argument("--kernel-steps", type=int, default=10,
-                    help="eager instrumented steps for kernel timing (only without --ring / hipGraphs)")
+                    help="--full: eager instrumented steps for kernel timing (only without --ring / hipGraphs)")
     ap.add_argument("--ring", type=int, default=0,
                     help="copies of the step graph with event-record nodes, replayed in turn in the timed "
                          "region; per-launch times are read from the last min(steps, ring) of them. ROCm 7 "
@@ -76,16 +93,16 @@ def parse():
                          "timed region replays it K / S times, every step complete); 1: one step per graph")
     ap.add_argument("--settle-steps", type=int, default=1000,
                     help="untimed steps after the warmup that bring the GPU to its sustained clock")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU baseline work")
-    ap.add_argument("--no-cpu", dest="cpu", action="store_false")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds of CPU baseline work")
+    ap.add_argument("--no-cpu", dest="cpu", action="store_false", help="--full: skip the CPU baselines")
     ap.add_argument("--no-legs", dest="legs", action="store_false",
-                    help="skip the other workloads (lego_dense, truck, fox) run after the headline at N=1")
+                    help="--full: skip the other workloads (lego_dense, truck, fox) run after the headline at N=1")
     ap.add_argument("--leg-steps", type=int, default=50)
     ap.add_argument("--leg-settle", type=int, default=300)
     ap.add_argument("--no-render", dest="render", action="store_false",
-                    help="skip the test-render speed (one full image per iteration) at N=1")
+                    help="--full: skip the test-render speed (one full image per iteration) at N=1")
     ap.add_argument("--no-dp-path", dest="dp_path", action="store_false",
-                    help="skip the data-parallel engine path measured on a one-rank RCCL group at N=1")
+                    help="--full: skip the data-parallel engine path measured on a one-rank RCCL group at N=1")
     ap.add_argument("--engine", choices=["fused", "autograd"], default="fused")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="lego",
                     help="lego: the headline (Config 2, Lego 800x800, box occupancy, ~19 samples/ray); "
@@ -133,6 +150,65 @@ class KernelTimer:
         torch.cuda.synchronize()
         ts = [s.elapsed_time(e) for s, e in self.pairs]
         return float(np.mean(ts)) if ts else float("nan")
+
+
+DUMP_TABLE_SAMPLE = 1 << 20  # hash-table values written per array (of 12.2M at log2T 19)
+
+
+def _f32(t):
+    return t.detach().float().cpu().numpy()
+
+
+def table_sample(n, dev):
+    """The hash-table values --dump-outputs writes: DUMP_TABLE_SAMPLE flat
+    indices drawn with a fixed seed of its own (the same for every run and
+    build; the global generators are left alone), sorted; None = all of them."""
+    if n <= DUMP_TABLE_SAMPLE:
+        return None
+    idx = np.sort(np.random.default_rng(0x6e6770).integers(0, n, DUMP_TABLE_SAMPLE))
+    return torch.from_numpy(idx).to(dev)
+
+
+def named_arrays(prefix, tensors, dev):
+    """{prefix_table, prefix_sigma_net, prefix_color_net: float32} of the
+    (table, sigma MLP, colour MLP) tensors, the table as table_sample picks it."""
+    out = {}
+    for name, t in zip(("table", "sigma_net", "color_net"), tensors):
+        t = t.detach().reshape(-1)
+        idx = table_sample(t.numel(), dev) if name == "table" else None
+        out[f"{prefix}_{name}"] = _f32(t if idx is None else t[idx])
+    return out
+
+
+def fused_step_outputs(ft):
+    """What the last FusedTrainer step left before its update is applied: the
+    step's (loss-scaled, fp16) gradient, which the Adam sweep clears, and the
+    per-ray loss and sample count, put in ray order (the march may emit the
+    rays in any order; rays[:, 0] is the ray each slot holds)."""
+    torch.cuda.synchronize()
+    out = named_arrays("grad", ft.grads, ft.dev)
+    rays = ft.rays.cpu().numpy()
+    loss_ray = _f32(ft.loss_ray)
+    n = rays.shape[0]
+    if np.array_equal(np.sort(rays[:, 0]), np.arange(n)):
+        order = np.argsort(rays[:, 0], kind="stable")
+        rays, loss_ray = rays[order], loss_ray[order]
+    out["ray_loss"] = loss_ray
+    out["ray_samples"] = rays[:, 2].astype(np.float32)
+    return out
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy, float32 or float64 each."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        total += a.nbytes
+        np.save(os.path.join(path, f"{name}.npy"), a)
+    assert total <= 64 << 20, total
 
 
 def launch_cmd(gpus, argv, port):
@@ -203,7 +279,11 @@ def main():
     if args.engine == "fused" and ft.live_fraction() is not None:
         # the backwards walk only these rows (the rest carry a zero gradient)
         result["live_rows_frac"] = round(ft.live_fraction(), 4)
-    if world == 1 and args.engine == "fused":
+    outputs = result.pop("outputs")
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, outputs)
+    del outputs
+    if args.full and world == 1 and args.engine == "fused":
         result["touched"] = touched_pairs(ft)
         ft.flush()
         if args.render:
@@ -215,7 +295,7 @@ def main():
             torch.cuda.empty_cache()
             result["legs"] = {w: run_leg(args, w, dev) for w in LEGS if w != args.workload}
 
-    if rank == 0 and world == 1 and args.cpu:
+    if args.full and rank == 0 and world == 1 and args.cpu:
         result["cpu_baseline"] = cpu_baseline(model, data, args)
 
     if rank == 0:
@@ -455,9 +535,6 @@ def _flat_total(log2T):
 
 def run_autograd(args, model, data, bits, world, dev):
     """The step through the reference-API autograd Functions (nerf/train.py)."""
-    import gridencoder.backend as gb
-    import ffmlp.backend as fb
-    import raymarching.backend as rb
     from nerf.train import Trainer
 
     trainer = Trainer(model, data, lr=1e-2, iters=30000, fp16=True, update_density=False,
@@ -512,8 +589,51 @@ def run_autograd(args, model, data, bits, world, dev):
     value = rays_total / elapsed
     samples = model.step_counter[:, 0].float()
     samples_per_step = int(samples[samples > 0].mean().item()) if (samples > 0).any() else 0
+    outputs = {}
+    if args.dump_outputs:  # the last step's loss, (loss-scaled) gradients and updated parameters
+        tensors = (model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights)
+        outputs["loss"] = np.array([float(loss.float().item())], np.float64)
+        outputs.update(named_arrays("param", tensors, dev))
+        if all(t.grad is not None for t in tensors):
+            outputs.update(named_arrays("grad", [t.grad for t in tensors], dev))
 
-    # -------- per-kernel HIP-event timing (eager steps, same shapes) --------
+    result = {
+        "metric": METRIC,
+        "value": round(value, 1),
+        "unit": "rays/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": round(value / PUBLISHED_V100_RAYS_PER_S, 3),
+        "dtype": "fp16",
+        "data": "synthetic",
+        "config": {
+            "num_rays_per_gpu": args.num_rays,
+            "global_batch_rays": args.num_rays * world,
+            "samples_per_step": samples_per_step,
+            "mean_count_M": mean_count,
+            "parallelism": f"dp{world}",
+            "hipgraph": used_graph,
+            "baseline_ref": "V100 97 it/s x 4096 rays (readme.md:211)",
+            "engine": "autograd",
+        },
+        "loss": float(loss.float().item()),
+        "outputs": outputs,
+    }
+    if args.full:
+        result.update(autograd_extras(args, trainer, model, bits, samples_per_step))
+    return result
+
+
+def autograd_extras(args, trainer, model, bits, samples_per_step):
+    """--full: per-kernel HIP-event timing (eager steps, same shapes), the
+    roofline of the longer grid kernel and the density-update cost."""
+    import gridencoder.backend as gb
+    import ffmlp.backend as fb
+    import raymarching.backend as rb
     trainer_graph, trainer_static = trainer.graph, trainer.static
     trainer.graph, trainer.static = None, None
     timers = {
@@ -550,28 +670,7 @@ def run_autograd(args, model, data, bits, world, dev):
     # density-grid update cost (reported, not in the timed step)
     density = density_update_times(model, bits)
 
-    result = {
-        "metric": METRIC,
-        "value": round(value, 1),
-        "unit": "rays/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": round(value / PUBLISHED_V100_RAYS_PER_S, 3),
-        "dtype": "fp16",
-        "data": "synthetic",
-        "config": {
-            "num_rays_per_gpu": args.num_rays,
-            "global_batch_rays": args.num_rays * world,
-            "samples_per_step": samples_per_step,
-            "mean_count_M": mean_count,
-            "parallelism": f"dp{world}",
-            "hipgraph": used_graph,
-            "baseline_ref": "V100 97 it/s x 4096 rays (readme.md:211)",
-        },
+    return {
         "roofline": {
             "kernel": dominant,
             "bound": "hbm",
@@ -589,11 +688,7 @@ def run_autograd(args, model, data, bits, world, dev):
                         "tflops": round(ffmlp_flops / (mlp_ms * 1e-3) / 1e12, 2) if mlp_ms > 0 else None,
                         "peak_tflops": FP16_MFMA_PEAK_TFLOPS},
         "density_update_ms": density,
-        "loss": float(loss.float().item()),
     }
-
-    result["config"]["engine"] = "autograd"
-    return result
 
 
 def adam_bytes(ft, groups=None):
@@ -786,36 +881,14 @@ def run_fused(args, model, data, bits, world, dev):
     value = args.num_rays * world * args.steps / elapsed
     samples = model.step_counter[:, 0].float()
     samples_per_step = int(samples[samples > 0].mean().item()) if (samples > 0).any() else 0
-    loss = ft.last_loss
-
-    # ---------------- per-launch device time (roofline) ----------------
-    groups = None
-    if world == 1:
-        kernel_ms, per_step, counts = ft.timed_body_steps(args.kernel_steps)
-        groups = ft.adam_groups()  # the pending update's (the last timed body step's gradient)
-    else:
-        ft.flush()
-        kernel_ms, per_step, counts = ft.timed_steps(args.kernel_steps, with_counts=True)
-    counts = [min(int(c), ft.M) for c in counts]
-    rows = float(np.mean(counts))
-    # the rows the backwards walk (options live_rows: those with a nonzero gradient)
-    lc = getattr(ft, "body_live_counts", None) if world == 1 else None
-    live = float(np.mean(lc)) if lc else None
+    outputs = fused_step_outputs(ft) if args.dump_outputs else {}
+    loss = ft.last_loss  # applies the last step's update (flush)
+    if args.dump_outputs:
+        outputs["loss"] = np.array([loss], np.float64)
+        outputs.update(named_arrays("param", ft.params, dev))
     grid = grid_roofline(grid_clock, args.steps, args.workload,
                          samples_per_step if getattr(ft, "_live", False) else None)
-    if world == 1:
-        roofline = launch_roofline(ft, kernel_ms, per_step, counts, args.num_rays, args.workload, live, groups)
-    else:  # the data-parallel step's phases include collectives: the grid backward names the roofline
-        roofline = grid
-    mlp_ms = sum(v for k, v in kernel_ms.items() if k.startswith("ffmlp"))
-    ffmlp_flops = 36864 * rows + 73728 * (rows if live is None else live)
-    step_bytes = whole_step_bytes(rows, args.num_rays, sum(p.numel() for p in model.parameters()),
-                                  int(model.encoder.embeddings.numel()), live)
-
-    density = density_update_times(model, bits, ft)
-    cadence = density_cadence(ft, bits, args) if world == 1 else None
-
-    return {
+    result = {
         "metric": METRIC,
         "value": round(value, 1),
         "unit": "rays/s",
@@ -843,9 +916,49 @@ def run_fused(args, model, data, bits, world, dev):
             "bound": float(model.bound),
             "baseline_ref": "V100 97 it/s x 4096 rays (readme.md:211)",
         },
-        "roofline": roofline,
         # north_star's grid_encode target, on the grid backward's own clock
+        # (stamped by the timed region's launches themselves); --full puts the
+        # step's longest launch in "roofline" instead
+        "roofline": grid,
         "roofline_grid_encode": grid,
+        "loss": loss,
+        "outputs": outputs,
+    }
+    if args.full:
+        result.update(fused_extras(args, ft, model, bits, world, grid, ms_per_step, samples_per_step))
+    return result, ft
+
+
+def fused_extras(args, ft, model, bits, world, grid, ms_per_step, samples_per_step):
+    """--full: the per-launch times and rooflines (eager steps of their own,
+    run right after the timed region) and the density-update figures."""
+    # ---------------- per-launch device time (roofline) ----------------
+    groups = None
+    if world == 1:
+        kernel_ms, per_step, counts = ft.timed_body_steps(args.kernel_steps)
+        groups = ft.adam_groups()  # the pending update's (the last timed body step's gradient)
+    else:
+        ft.flush()
+        kernel_ms, per_step, counts = ft.timed_steps(args.kernel_steps, with_counts=True)
+    counts = [min(int(c), ft.M) for c in counts]
+    rows = float(np.mean(counts))
+    # the rows the backwards walk (options live_rows: those with a nonzero gradient)
+    lc = getattr(ft, "body_live_counts", None) if world == 1 else None
+    live = float(np.mean(lc)) if lc else None
+    if world == 1:
+        roofline = launch_roofline(ft, kernel_ms, per_step, counts, args.num_rays, args.workload, live, groups)
+    else:  # the data-parallel step's phases include collectives: the grid backward names the roofline
+        roofline = grid
+    mlp_ms = sum(v for k, v in kernel_ms.items() if k.startswith("ffmlp"))
+    ffmlp_flops = 36864 * rows + 73728 * (rows if live is None else live)
+    step_bytes = whole_step_bytes(rows, args.num_rays, sum(p.numel() for p in model.parameters()),
+                                  int(model.encoder.embeddings.numel()), live)
+
+    density = density_update_times(model, bits, ft)
+    cadence = density_cadence(ft, bits, args) if world == 1 else None
+
+    return {
+        "roofline": roofline,
         "kernels_ms": {k: round(v, 5) for k, v in kernel_ms.items()},
         "kernel_samples": counts,
         "kernel_live_rows": lc or None,
@@ -860,8 +973,7 @@ def run_fused(args, model, data, bits, world, dev):
         # beside the headline (which SURVEY §8(d) defines without it): upstream's
         # density-grid cadence timed end to end, one partial update per 16 steps
         "with_density_update": cadence,
-        "loss": loss,
-    }, ft
+    }
 
 
 def density_cadence(ft, bits, args, cycles=6, every=16):

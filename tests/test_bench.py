@@ -85,6 +85,67 @@ def test_fox_leg_occupancy_is_not_degenerate():
     assert total / (2 * 2048) >= 20, total / 4096
 
 
+def test_dump_arrays_are_float_and_the_table_sample_is_fixed(tmp_path):
+    """--dump-outputs writes DIR/<name>.npy as float32 / float64, and the hash
+    table goes out as the same seeded sample of its values in every run (drawn
+    without touching numpy's global generator, which the batches use)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    np.random.seed(5)
+    before = np.random.get_state()[1].copy()
+    a, b = bench.table_sample(12239728, "cpu"), bench.table_sample(12239728, "cpu")
+    assert np.array_equal(before, np.random.get_state()[1])
+    assert torch.equal(a, b) and a.numel() == bench.DUMP_TABLE_SAMPLE
+    assert int(a.min()) >= 0 and int(a.max()) < 12239728 and bool((a[1:] >= a[:-1]).all())
+    assert bench.table_sample(7168, "cpu") is None
+    tensors = [torch.arange(12239728, dtype=torch.float32), torch.ones(7168, dtype=torch.float16),
+               torch.zeros(11264)]
+    arrays = bench.named_arrays("param", tensors, "cpu")
+    assert sorted(arrays) == ["param_color_net", "param_sigma_net", "param_table"]
+    assert np.array_equal(arrays["param_table"], a.numpy().astype(np.float32))
+    arrays["ray_samples"] = np.arange(5, dtype=np.int32)
+    bench.write_outputs(str(tmp_path / "out"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert sorted(got) == sorted(arrays)
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert np.array_equal(got["ray_samples"], np.arange(5)) and got["param_sigma_net"].shape == (7168,)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K` times exactly K steps, prints the
+    headline with ms_per_step and none of the --full measurements, and with
+    --dump-outputs leaves the last step's arrays as float .npy files."""
+    import numpy as np
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--settle-steps", "4", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 7 and out["n_gpus"] == 1 and out["unit"] == "rays/s" and out["dtype"] == "fp16"
+    assert out["higher_is_better"] is True and "metric" in out
+    assert out["ms_per_step"] > 0
+    # value = rays per step / the step time (ms_per_step is rounded to 1e-4 ms)
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 / 4096 - 1) <= 1e-4 / out["ms_per_step"] + 1e-6
+    assert not {"cpu_baseline", "legs", "render", "dp_path", "touched", "kernels_ms", "density_update_ms",
+                "with_density_update"} & set(out)
+    got = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert sorted(got) == ["grad_color_net", "grad_sigma_net", "grad_table", "loss", "param_color_net",
+                           "param_sigma_net", "param_table", "ray_loss", "ray_samples"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    # (the loss-scaled fp16 gradient may overflow in the first steps: the scaler then skips the update)
+    assert all(np.isfinite(v).all() for k, v in got.items() if not k.startswith("grad_"))
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert float(got["loss"][0]) == out["loss"] and got["ray_loss"].shape == (4096,)
+    assert got["ray_samples"].sum() > 0 and np.count_nonzero(got["grad_sigma_net"]) > 0
+    assert np.count_nonzero(got["param_table"]) > 0
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("exchange", ["zero1", "sparse"])
 def test_bench_gpus2_gloo_runs_two_ranks(exchange):

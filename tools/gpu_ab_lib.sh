@@ -17,7 +17,7 @@ fi
 for w in ${WORKLOADS:-lego}; do
     for i in $(seq 1 ${ROUNDS:-2}); do
         for v in base "$@"; do
-            NGP_HIP_LIB=$(lib $v) timeout -k 10 200 python -u bench.py --no-cpu --workload $w --steps 200 --warmup 20 \
+            NGP_HIP_LIB=$(lib $v) timeout -k 10 200 python -u bench.py --full --no-cpu --workload $w --steps 200 --warmup 20 \
                 > $O/${w}_$v$i.json 2> $O/${w}_$v$i.err
             python -c "import json; d=json.load(open('$O/${w}_$v$i.json')); r=d['roofline']; print('$w', '$v', $i, d['value'], d['ms_per_step'], 'gbwd', r['avg_launch_ms'], r['frac'], {k: round(v * 1000, 1) for k, v in d['kernels_ms'].items()})" | tee -a $O/ab.txt
         done

@@ -21,7 +21,7 @@ for KNOB in $KNOBS; do
     for v in 0 1; do
       ENVS=""
       for K in ${KNOB//+/ }; do ENVS="$ENVS $K=$v"; done
-      env $ENVS timeout -k 10 200 python -u bench.py --no-cpu --no-legs --no-dp-path --no-render --steps 200 \
+      env $ENVS timeout -k 10 200 python -u bench.py --full --no-cpu --no-legs --no-dp-path --no-render --steps 200 \
           > $O/ab_${KNOB}_${v}_${rep}.json 2> $O/ab_${KNOB}_${v}_${rep}.err
     done
   done

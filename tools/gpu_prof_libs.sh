@@ -11,7 +11,7 @@ lib() { if [ "$1" = base ]; then echo torch-ngp_amd/libngp_hip.so; else echo tor
 for w in ${WORKLOADS:-lego}; do
     for v in base "$@"; do
         NGP_HIP_LIB=$(lib $v) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${w}_$v -o run -- \
-            python3 bench.py --no-cpu --workload $w --steps 100 --warmup 10 > $O/${w}_$v.log 2>&1
+            python3 bench.py --full --no-cpu --workload $w --steps 100 --warmup 10 > $O/${w}_$v.log 2>&1
         f=$(find $O/${w}_$v -name run_kernel_stats.csv | sort | tail -n 1)
         python3 - "$f" "$w" "$v" <<'PY' | tee -a $O/prof.txt
 import csv, sys
