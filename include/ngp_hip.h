@@ -16,7 +16,8 @@
  *     NGP_ERR_ARG / NGP_ERR_UNSUPPORTED mirror the reference's TORCH_CHECK /
  *     std::runtime_error("... must be ...") failures; the Python shims raise
  *     RuntimeError with the reference's wording.
- *   - dtype codes: NGP_DTYPE_F32 = 0, NGP_DTYPE_F16 = 1, NGP_DTYPE_F64 = 2.
+ *   - dtype codes: NGP_DTYPE_F32 = 0, NGP_DTYPE_F16 = 1, NGP_DTYPE_F64 = 2;
+ *     NGP_DTYPE_U8 = 3 (the image source's pixels only).
  */
 #ifndef NGP_HIP_H
 #define NGP_HIP_H
@@ -36,6 +37,7 @@ extern "C" {
 #define NGP_DTYPE_F32 0
 #define NGP_DTYPE_F16 1
 #define NGP_DTYPE_F64 2
+#define NGP_DTYPE_U8 3
 
 /* Library identification: ABI version (bumped on any signature change). */
 int ngp_abi_version(void);
@@ -439,6 +441,58 @@ int ngp_grid_encode_backward_fused_reduce_batch_live(
     size_t workspace_bytes, int32_t grad_layout, int32_t* nonfinite, int32_t n_nets, void* const* mlp_workspaces,
     const uint32_t* mlp_Bs, const uint32_t* in_dims, const uint32_t* hidden_dims, const uint32_t* num_layers,
     void* const* grad_weights, int32_t* mlp_nonfinite, const ngp_batch_job* job, void* stream);
+/* The fused step's batch drawn from an image dataset instead of the analytic
+ * boxes (the reference's training collate, nerf/provider.py:442-508, with
+ * preloaded images): ray n of a draw takes its RGBA target from
+ * pixels[pose][pix], everything else (pose, pixel, ray, background, march
+ * noise, near/far, the counter bookkeeping) as ngp_lego_rays draws it from the
+ * same counter-RNG streams, so the same seed, poses and intrinsics give the
+ * same rays bit for bit.
+ *   pixels: [n_poses, H, W, channels], dtype NGP_DTYPE_U8 (converted as
+ *     (float)v / 255.0f, a true division) or NGP_DTYPE_F32; RGBA pixels are
+ *     one load each, so 4-byte (uint8) / 16-byte (float32) aligned.
+ *   channels 4: RGBA target, random background (as ngp_lego_rays);
+ *   channels 3: target (r, g, b, 1) and background (1, 1, 1): the reference's
+ *     bg_color = 1 for 3-channel images (nerf/utils.py:508-509); the loss's
+ *     blend rgb * 1 + 1 * 0 then reproduces gt_rgb = images exactly.
+ *   pix (nullable) i32 [N]: each ray's flat pixel index j * W + i (the
+ *     reference's results['inds'], nerf/utils.py:112);
+ *   image_index (nullable) i32 [1]: the draw's image.
+ * Bad channels / dtype / null pixels: NGP_ERR_ARG before any device work. */
+typedef struct ngp_image_source {
+    const void* pixels;
+    uint32_t channels;
+    int32_t dtype;
+    int32_t* pix;
+    int32_t* image_index;
+} ngp_image_source;
+/* ngp_lego_rays with the image source in place of the boxes. */
+int ngp_image_rays(const float* poses, uint32_t n_poses, const float* intrinsics4, uint32_t H, uint32_t W,
+                   uint32_t N, const ngp_image_source* src, const float* aabb6, float min_near, uint32_t seed,
+                   void* state, float* rays_o, float* rays_d, float* rgba, float* bg, float* nears, float* fars,
+                   float* noises, int32_t* counter, int32_t* step_counter, void* stream);
+/* ngp_fused_step_head with the image source in place of the boxes. */
+int ngp_fused_step_head_images(const float* poses, uint32_t n_poses, const float* intrinsics4, uint32_t H,
+                               uint32_t W, uint32_t N, const ngp_image_source* src, const float* aabb6,
+                               float min_near, uint32_t seed, void* state, float* rays_o, float* rays_d,
+                               float* rgba, float* bg, float* nears, float* fars, float* noises, int32_t* counter,
+                               int32_t* step_counter, float growth_factor, float backoff_factor,
+                               int32_t growth_interval, int32_t scaler_enabled, const float* loss_ray,
+                               int32_t n_nets, const void* const* mlp_weights, const uint32_t* in_dims,
+                               const uint32_t* hidden_dims, const uint32_t* num_layers, void* const* images,
+                               void* clear, uint32_t clear_bytes, void* stream);
+/* ngp_grid_encode_backward_fused_reduce_batch_live whose next batch (job) is
+ * drawn from the image source (job->boxes null, job->nboxes 0). live_rows
+ * null: every row below *live_count, the marcher's sample count
+ * (ngp_grid_encode_backward_fused_reduce_batch). */
+int ngp_grid_encode_backward_fused_reduce_batch_images(
+    const void* grad, const float* xyz, float bound, const int32_t* offsets, void* grad_embeddings, uint32_t B,
+    const int32_t* live_rows, const int32_t* live_count, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+    uint32_t gridtype, int32_t align_corners, uint32_t interp, const int32_t* offsets_host, void* workspace,
+    size_t workspace_bytes, int32_t grad_layout, int32_t* nonfinite, int32_t n_nets, void* const* mlp_workspaces,
+    const uint32_t* mlp_Bs, const uint32_t* in_dims, const uint32_t* hidden_dims, const uint32_t* num_layers,
+    void* const* grad_weights, int32_t* mlp_nonfinite, const ngp_batch_job* job, const ngp_image_source* src,
+    void* stream);
 /* ngp_grid_encode_forward_fused (out_layout 0) with the fused step's tail as
  * extra workgroups dispatched first: the deferred GradScaler / LambdaLR / loss
  * bookkeeping of the update the march launch applied (state; when pending) and

@@ -130,6 +130,15 @@ SIGNATURES = {
     "ngp_fused_state_init": [c_vp, c_f32, c_vp],
     "ngp_lego_rays": [c_vp, c_u32, c_vp, c_u32, c_u32, c_u32, c_vp, c_i32, c_vp, c_f32, c_u32,
                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_image_rays": [c_vp, c_u32, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_f32, c_u32,
+                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_fused_step_head_images": [c_vp, c_u32, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_f32, c_u32, c_vp,
+                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_i32, c_i32,
+                                   c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp],
+    "ngp_grid_encode_backward_fused_reduce_batch_images": [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_vp, c_vp,
+                                                           c_u32, c_u32, c_u32, c_f32, c_u32, c_u32, c_i32, c_u32,
+                                                           c_vp, c_vp, c_sz, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_nerf_glue_forward": [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_vp, c_vp],
     "ngp_nerf_glue_backward": [c_vp, c_vp, c_u32, c_vp, c_vp],
     "ngp_nerf_composite_loss": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
@@ -184,6 +193,7 @@ _RESTYPES = {
 }
 
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}
+DTYPE_U8 = 3  # NGP_DTYPE_U8: the image source's pixels only
 DENSITY_STATS_LEN = 1025  # include/ngp_hip.h NGP_DENSITY_STATS_LEN (doubles of ngp_density_grid_ema_pack's stats)
 
 
@@ -208,6 +218,13 @@ class BatchJob(ctypes.Structure):
                 ("N", c_u32), ("boxes", c_vp), ("nboxes", c_i32), ("aabb6", c_vp), ("min_near", c_f32),
                 ("seed", c_u32), ("state", c_vp), ("rays_o", c_vp), ("rays_d", c_vp), ("rgba", c_vp), ("bg", c_vp),
                 ("nears", c_vp), ("fars", c_vp), ("noises", c_vp), ("counter", c_vp), ("step_counter", c_vp)]
+
+
+class ImageSource(ctypes.Structure):
+    """ngp_image_source (include/ngp_hip.h): the pixel stack the fused step's
+    batch takes its targets from, and the draw's pixel / image indices."""
+    _fields_ = [("pixels", c_vp), ("channels", c_u32), ("dtype", c_i32), ("pix", c_vp), ("image_index", c_vp)]
+
 
 _lib = None
 

@@ -2834,7 +2834,8 @@ static int reduce_batch_impl(
     int32_t align_corners, uint32_t interp, const int32_t* offsets_host, void* workspace, size_t workspace_bytes,
     int32_t grad_layout, int32_t* nonfinite, int32_t n_nets, void* const* mlp_workspaces, const uint32_t* mlp_Bs,
     const uint32_t* in_dims, const uint32_t* hidden_dims, const uint32_t* num_layers, void* const* grad_weights,
-    int32_t* mlp_nonfinite, const ngp_batch_job* job, void* stream, const int32_t* rows) {
+    int32_t* mlp_nonfinite, const ngp_batch_job* job, void* stream, const int32_t* rows,
+    const ngp_image_source* src = nullptr) {
     NGP_REQUIRE(job && job->state && job->counter && job->poses && job->N > 0 && job->n_poses > 0, NGP_ERR_ARG,
                 "grid_encode_backward_fused_reduce_batch: incomplete batch job");
     NGP_REQUIRE(job->nboxes >= 0 && job->nboxes <= ngp_head::kMaxBoxes, NGP_ERR_ARG,
@@ -2848,6 +2849,7 @@ static int reduce_batch_impl(
                                  job->aabb6, job->min_near, job->seed);
     bl.out = ngp_head::LegoOut{job->rays_o, job->rays_d, job->rgba, job->bg, job->nears, job->fars, job->noises,
                                job->counter, job->step_counter, 1};
+    if (src) ngp_head::set_image_source(bl.sc, bl.out, src);  // (checked by the caller)
     bl.poses = job->poses;
     bl.st = static_cast<ngp_step::StepState*>(job->state);
     bl.N = job->N;
@@ -2898,6 +2900,23 @@ extern "C" int ngp_grid_encode_backward_fused_reduce_batch_live(
                              align_corners, interp, offsets_host, workspace, workspace_bytes, grad_layout, nonfinite,
                              n_nets, mlp_workspaces, mlp_Bs, in_dims, hidden_dims, num_layers, grad_weights,
                              mlp_nonfinite, job, stream, live_rows);
+}
+
+extern "C" int ngp_grid_encode_backward_fused_reduce_batch_images(
+    const void* grad, const float* xyz, float bound, const int32_t* offsets, void* grad_embeddings, uint32_t B,
+    const int32_t* live_rows, const int32_t* live_count, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+    uint32_t gridtype, int32_t align_corners, uint32_t interp, const int32_t* offsets_host, void* workspace,
+    size_t workspace_bytes, int32_t grad_layout, int32_t* nonfinite, int32_t n_nets, void* const* mlp_workspaces,
+    const uint32_t* mlp_Bs, const uint32_t* in_dims, const uint32_t* hidden_dims, const uint32_t* num_layers,
+    void* const* grad_weights, int32_t* mlp_nonfinite, const ngp_batch_job* job, const ngp_image_source* src,
+    void* stream) {
+    if (int e = ngp_head::check_image_source(src, "grid_encode_backward_fused_reduce_batch_images")) return e;
+    NGP_REQUIRE(!job || (!job->boxes && job->nboxes == 0), NGP_ERR_ARG,
+                "grid_encode_backward_fused_reduce_batch_images: an image job carries no boxes");
+    return reduce_batch_impl(grad, xyz, bound, offsets, grad_embeddings, B, live_count, D, C, L, S, H, gridtype,
+                             align_corners, interp, offsets_host, workspace, workspace_bytes, grad_layout, nonfinite,
+                             n_nets, mlp_workspaces, mlp_Bs, in_dims, hidden_dims, num_layers, grad_weights,
+                             mlp_nonfinite, job, stream, live_rows, src);
 }
 
 #ifdef NGP_STAMPS

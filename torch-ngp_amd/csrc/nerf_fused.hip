@@ -647,6 +647,22 @@ extern "C" int ngp_lego_rays(const float* poses, uint32_t n_poses, const float* 
     return ngp_check_launch("lego_rays");
 }
 
+extern "C" int ngp_image_rays(const float* poses, uint32_t n_poses, const float* intrinsics4, uint32_t H,
+                              uint32_t W, uint32_t N, const ngp_image_source* src, const float* aabb6,
+                              float min_near, uint32_t seed, void* state, float* rays_o, float* rays_d,
+                              float* rgba, float* bg, float* nears, float* fars, float* noises, int32_t* counter,
+                              int32_t* step_counter, void* stream) {
+    if (int e = check_image_source(src, "image_rays")) return e;
+    NGP_REQUIRE(n_poses > 0 && H > 0 && W > 0, NGP_ERR_ARG, "image_rays: empty pose set or image");
+    LegoScene sc = make_scene(n_poses, intrinsics4, H, W, nullptr, 0, aabb6, min_near, seed);
+    LegoOut out{rays_o, rays_d, rgba, bg, nears, fars, noises, counter, step_counter};
+    set_image_source(sc, out, src);
+    if (N == 0) return NGP_OK;
+    k_lego_rays<<<ngp_div_up(N, 256), 256, 0, ngp_stream(stream)>>>(poses, sc, N, static_cast<StepState*>(state),
+                                                                     out);
+    return ngp_check_launch("image_rays");
+}
+
 extern "C" int ngp_nerf_glue_forward(const void* h_sigma, const float* dirs, float density_scale,
                                      float* sigma, void* color_in, uint32_t B, const int32_t* count,
                                      void* stream) {
@@ -747,6 +763,37 @@ extern "C" int ngp_fused_optimizer_update(int32_t n_tensors, float* const* param
                             nullptr, state, stream, true);
 }
 
+namespace {
+// ngp_fused_step_head / ngp_fused_step_head_images: the scene's batch source is the only difference
+int step_head_launch(const float* poses, uint32_t n_poses, const float* intrinsics4, uint32_t H, uint32_t W,
+                     uint32_t N, const float* boxes, int32_t nboxes, const ngp_image_source* src,
+                     const float* aabb6, float min_near, uint32_t seed, void* state, float* rays_o, float* rays_d,
+                     float* rgba, float* bg, float* nears, float* fars, float* noises, int32_t* counter,
+                     int32_t* step_counter, float growth_factor, float backoff_factor, int32_t growth_interval,
+                     int32_t scaler_enabled, const float* loss_ray, int32_t n_nets, const void* const* mlp_weights,
+                     const uint32_t* in_dims, const uint32_t* hidden_dims, const uint32_t* num_layers,
+                     void* const* images, void* clear, uint32_t clear_bytes, void* stream) {
+    NGP_REQUIRE(nboxes >= 0 && nboxes <= kMaxBoxes, NGP_ERR_ARG, "step_head: at most %d boxes", kMaxBoxes);
+    NGP_REQUIRE(n_poses > 0 && H > 0 && W > 0 && N > 0, NGP_ERR_ARG, "step_head: empty pose set, image or batch");
+    NGP_REQUIRE(state && loss_ray, NGP_ERR_ARG, "step_head: null state or loss_ray");
+    NGP_REQUIRE(clear_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(clear) & 15) == 0, NGP_ERR_ARG,
+                "step_head: clear must be 16-byte aligned, a multiple of 16 bytes");
+    ngp_pack::PackJobs jobs{};
+    if (n_nets > 0)
+        if (int e = ngp_pack::build_jobs(n_nets, mlp_weights, in_dims, hidden_dims, num_layers, images, jobs))
+            return e;
+    LegoScene sc = make_scene(n_poses, intrinsics4, H, W, boxes, nboxes, aabb6, min_near, seed);
+    LegoOut out{rays_o, rays_d, rgba, bg, nears, fars, noises, counter, step_counter};
+    if (src) set_image_source(sc, out, src);  // (checked by the caller)
+    const ScalerArgs sa{growth_factor, backoff_factor, growth_interval, scaler_enabled, 1.0f / (float)N};
+    const uint32_t nlego = ngp_div_up(N, 256);
+    k_step_head<<<nlego + 1 + (uint32_t)jobs.n, 256, 0, ngp_stream(stream)>>>(
+        poses, sc, N, static_cast<StepState*>(state), out, nlego, sa, loss_ray, jobs, static_cast<uint4*>(clear),
+        clear ? clear_bytes / 16 : 0u);
+    return ngp_check_launch("fused_step_head");
+}
+}  // namespace
+
 extern "C" int ngp_fused_step_head(const float* poses, uint32_t n_poses, const float* intrinsics4, uint32_t H,
                                    uint32_t W, uint32_t N, const float* boxes, int32_t nboxes, const float* aabb6,
                                    float min_near, uint32_t seed, void* state, float* rays_o, float* rays_d,
@@ -757,23 +804,27 @@ extern "C" int ngp_fused_step_head(const float* poses, uint32_t n_poses, const f
                                    const uint32_t* in_dims, const uint32_t* hidden_dims,
                                    const uint32_t* num_layers, void* const* images, void* clear,
                                    uint32_t clear_bytes, void* stream) {
-    NGP_REQUIRE(nboxes >= 0 && nboxes <= kMaxBoxes, NGP_ERR_ARG, "step_head: at most %d boxes", kMaxBoxes);
-    NGP_REQUIRE(n_poses > 0 && H > 0 && W > 0 && N > 0, NGP_ERR_ARG, "step_head: empty pose set, image or batch");
-    NGP_REQUIRE(state && loss_ray, NGP_ERR_ARG, "step_head: null state or loss_ray");
-    NGP_REQUIRE(clear_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(clear) & 15) == 0, NGP_ERR_ARG,
-                "step_head: clear must be 16-byte aligned, a multiple of 16 bytes");
-    ngp_pack::PackJobs jobs{};
-    if (n_nets > 0)
-        if (int e = ngp_pack::build_jobs(n_nets, mlp_weights, in_dims, hidden_dims, num_layers, images, jobs))
-            return e;
-    const LegoScene sc = make_scene(n_poses, intrinsics4, H, W, boxes, nboxes, aabb6, min_near, seed);
-    const LegoOut out{rays_o, rays_d, rgba, bg, nears, fars, noises, counter, step_counter};
-    const ScalerArgs sa{growth_factor, backoff_factor, growth_interval, scaler_enabled, 1.0f / (float)N};
-    const uint32_t nlego = ngp_div_up(N, 256);
-    k_step_head<<<nlego + 1 + (uint32_t)jobs.n, 256, 0, ngp_stream(stream)>>>(
-        poses, sc, N, static_cast<StepState*>(state), out, nlego, sa, loss_ray, jobs, static_cast<uint4*>(clear),
-        clear ? clear_bytes / 16 : 0u);
-    return ngp_check_launch("fused_step_head");
+    return step_head_launch(poses, n_poses, intrinsics4, H, W, N, boxes, nboxes, nullptr, aabb6, min_near, seed,
+                            state, rays_o, rays_d, rgba, bg, nears, fars, noises, counter, step_counter,
+                            growth_factor, backoff_factor, growth_interval, scaler_enabled, loss_ray, n_nets,
+                            mlp_weights, in_dims, hidden_dims, num_layers, images, clear, clear_bytes, stream);
+}
+
+extern "C" int ngp_fused_step_head_images(const float* poses, uint32_t n_poses, const float* intrinsics4, uint32_t H,
+                                          uint32_t W, uint32_t N, const ngp_image_source* src, const float* aabb6,
+                                          float min_near, uint32_t seed, void* state, float* rays_o, float* rays_d,
+                                          float* rgba, float* bg, float* nears, float* fars, float* noises,
+                                          int32_t* counter, int32_t* step_counter, float growth_factor,
+                                          float backoff_factor, int32_t growth_interval, int32_t scaler_enabled,
+                                          const float* loss_ray, int32_t n_nets, const void* const* mlp_weights,
+                                          const uint32_t* in_dims, const uint32_t* hidden_dims,
+                                          const uint32_t* num_layers, void* const* images, void* clear,
+                                          uint32_t clear_bytes, void* stream) {
+    if (int e = check_image_source(src, "step_head_images")) return e;
+    return step_head_launch(poses, n_poses, intrinsics4, H, W, N, nullptr, 0, src, aabb6, min_near, seed, state,
+                            rays_o, rays_d, rgba, bg, nears, fars, noises, counter, step_counter, growth_factor,
+                            backoff_factor, growth_interval, scaler_enabled, loss_ray, n_nets, mlp_weights, in_dims,
+                            hidden_dims, num_layers, images, clear, clear_bytes, stream);
 }
 
 extern "C" int ngp_fused_optimizer_update_head(

@@ -38,6 +38,11 @@ struct LegoScene {
     float aabb[6];
     float min_near;
     uint32_t seed;
+    // image source (ngp_image_source): pixels [n_poses, H, W, channels], uint8
+    // or float32; null = the analytic boxes above
+    const void* pixels;
+    uint32_t channels;
+    int32_t pix_dtype;
 };
 
 // near/far against the aabb, reference raymarching.cu:91-145 (same as
@@ -68,6 +73,9 @@ struct LegoOut {
     // counter (the next batch drawn in the grid backward's bin launch): its
     // counts are recorded but the counter is left to the accumulate to reset
     int32_t keep_counter;
+    // image source only, nullable: each ray's flat pixel index j * W + i (the
+    // reference's results['inds'], utils.py:112) and the draw's image
+    int32_t *pix, *image_index;
 };
 
 static inline LegoScene make_scene(uint32_t n_poses, const float* intrinsics4, uint32_t H, uint32_t W,
@@ -87,6 +95,69 @@ static inline LegoScene make_scene(uint32_t n_poses, const float* intrinsics4, u
     sc.min_near = min_near;
     sc.seed = seed;
     return sc;
+}
+
+// An image scene: the boxes scene of the same cameras with its targets taken
+// from a pixel stack. Argument checks of the image entries (before any device
+// work; they need no other argument): 0 or the error code.
+static inline int check_image_source(const ngp_image_source* src, const char* who) {
+    NGP_REQUIRE(src && src->pixels, NGP_ERR_ARG, "%s: null image source or pixels", who);
+    NGP_REQUIRE(src->channels == 3 || src->channels == 4, NGP_ERR_ARG, "%s: %u channels (RGB or RGBA images)", who,
+                src->channels);
+    NGP_REQUIRE(src->dtype == NGP_DTYPE_U8 || src->dtype == NGP_DTYPE_F32, NGP_ERR_ARG,
+                "%s: pixel dtype %d (NGP_DTYPE_U8 or NGP_DTYPE_F32)", who, src->dtype);
+    // RGBA pixels are read with one load each; float RGB with three 4-byte loads
+    const uintptr_t align = src->dtype == NGP_DTYPE_F32 ? (src->channels == 4 ? 16 : 4) : (src->channels == 4 ? 4 : 1);
+    NGP_REQUIRE((reinterpret_cast<uintptr_t>(src->pixels) & (align - 1)) == 0, NGP_ERR_ARG,
+                "%s: pixels must be %u-byte aligned", who, (unsigned)align);
+    return NGP_OK;
+}
+// A checked source into the scene and the draw's outputs.
+static inline void set_image_source(LegoScene& sc, LegoOut& out, const ngp_image_source* src) {
+    sc.nboxes = 0;
+    sc.pixels = src->pixels;
+    sc.channels = src->channels;
+    sc.pix_dtype = src->dtype;
+    out.pix = src->pix;
+    out.image_index = src->image_index;
+}
+
+// The image source's target of pixel `pix` of image `pose`: RGBA as stored
+// (uint8: v / 255, a true division, numpy's np.float32(v) / 255 bit for bit);
+// RGB: alpha 1 on a white background (the reference's bg_color = 1 for
+// 3-channel images, utils.py:508-509), so the loss's blend v * 1 + 1 * 0 is v.
+// Returns whether the background was set (RGB).
+NGP_DEV bool image_target(uint32_t n, uint32_t pose, uint32_t pix, const LegoScene& sc, const LegoOut& out) {
+    const size_t px = (size_t)pose * ((size_t)sc.H * sc.W) + pix;  // past 2^32 elements on large stacks
+    float r, g, b, a = 1.0f;
+    if (sc.pix_dtype == NGP_DTYPE_U8) {
+        uint32_t c0, c1, c2, c3 = 255u;
+        if (sc.channels == 4) {
+            const uint32_t w = static_cast<const uint32_t*>(sc.pixels)[px];
+            c0 = w & 255u; c1 = (w >> 8) & 255u; c2 = (w >> 16) & 255u; c3 = w >> 24;
+        } else {
+            const uint8_t* q = static_cast<const uint8_t*>(sc.pixels) + px * 3;
+            c0 = q[0]; c1 = q[1]; c2 = q[2];
+        }
+        r = (float)c0 / 255.0f; g = (float)c1 / 255.0f; b = (float)c2 / 255.0f;
+        if (sc.channels == 4) a = (float)c3 / 255.0f;
+    } else if (sc.channels == 4) {
+        const float4 v = static_cast<const float4*>(sc.pixels)[px];
+        r = v.x; g = v.y; b = v.z; a = v.w;
+    } else {
+        const float* q = static_cast<const float*>(sc.pixels) + px * 3;
+        r = q[0]; g = q[1]; b = q[2];
+    }
+    out.rgba[n * 4 + 0] = r;
+    out.rgba[n * 4 + 1] = g;
+    out.rgba[n * 4 + 2] = b;
+    out.rgba[n * 4 + 3] = a;
+    if (out.pix) out.pix[n] = (int32_t)pix;
+    if (out.image_index && n == 0) out.image_index[0] = (int32_t)pose;
+    if (sc.channels == 4) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out.bg[n * 3 + k] = 1.0f;
+    return true;
 }
 
 // Ray n of draw `it` (the fused sampler, reference get_rays utils.py:52-136 +
@@ -110,26 +181,34 @@ NGP_DEV void lego_ray(uint32_t n, uint32_t it, const float* __restrict__ poses, 
         out.rays_o[n * 3 + k] = o[k];
         out.rays_d[n * 3 + k] = d[k];
     }
-    // analytic RGBA: colour of the nearest box hit (SyntheticLego.target)
-    float best = INFINITY;
-    int arg = -1;
-    for (int b = 0; b < sc.nboxes; ++b) {
-        float tn = -INFINITY, tf = INFINITY;
+    // the target: the pixel of the image stack (uniform across the launch) or
+    // the analytic RGBA, the colour of the nearest box hit (SyntheticLego.target)
+    bool bg_set = false;
+    if (sc.pixels) {
+        bg_set = image_target(n, pose, pix, sc, out);
+    } else {
+        float best = INFINITY;
+        int arg = -1;
+        for (int b = 0; b < sc.nboxes; ++b) {
+            float tn = -INFINITY, tf = INFINITY;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float inv = 1.0f / d[k];
-            const float t0 = (sc.lo[b][k] - o[k]) * inv, t1 = (sc.hi[b][k] - o[k]) * inv;
-            tn = fmaxf(tn, fminf(t0, t1));
-            tf = fminf(tf, fmaxf(t0, t1));
+            for (int k = 0; k < 3; ++k) {
+                const float inv = 1.0f / d[k];
+                const float t0 = (sc.lo[b][k] - o[k]) * inv, t1 = (sc.hi[b][k] - o[k]) * inv;
+                tn = fmaxf(tn, fminf(t0, t1));
+                tf = fminf(tf, fmaxf(t0, t1));
+            }
+            if (tf >= tn && tf > 0 && tn < best) { best = tn; arg = b; }
         }
-        if (tf >= tn && tf > 0 && tn < best) { best = tn; arg = b; }
+        out.rgba[n * 4 + 0] = arg >= 0 ? sc.rgb[arg][0] : 0.0f;
+        out.rgba[n * 4 + 1] = arg >= 0 ? sc.rgb[arg][1] : 0.0f;
+        out.rgba[n * 4 + 2] = arg >= 0 ? sc.rgb[arg][2] : 0.0f;
+        out.rgba[n * 4 + 3] = arg >= 0 ? 1.0f : 0.0f;
     }
-    out.rgba[n * 4 + 0] = arg >= 0 ? sc.rgb[arg][0] : 0.0f;
-    out.rgba[n * 4 + 1] = arg >= 0 ? sc.rgb[arg][1] : 0.0f;
-    out.rgba[n * 4 + 2] = arg >= 0 ? sc.rgb[arg][2] : 0.0f;
-    out.rgba[n * 4 + 3] = arg >= 0 ? 1.0f : 0.0f;
+    if (!bg_set) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out.bg[n * 3 + k] = rng_unit(sc.seed, it, n, 2 + k);
+        for (int k = 0; k < 3; ++k) out.bg[n * 3 + k] = rng_unit(sc.seed, it, n, 2 + k);
+    }
     noise = rng_unit(sc.seed, it, n, 5);
     out.noises[n] = noise;
     near_far(o, d, sc.aabb, sc.min_near, nr, fr);

@@ -1,0 +1,135 @@
+"""Train a scene on the fused engine: `python main_nerf.py <scene> -O`.
+
+The reference's entry point (main_nerf.py:6-103, 105-230) for the instant-ngp
+configuration (-O: fp16, cuda_ray, preloaded images), with its flag names and
+defaults, on nerf.fused.FusedTrainer: the images stay on the device as uint8
+and every batch is gathered there (the engine's image source), the steps
+between two density-grid updates replay as captured graphs, and nothing syncs
+with the host per step.
+
+Not here: --error_map importance sampling, patch sampling,
+--color_space linear, depth supervision, more than one image per batch."""
+import argparse
+import math
+import os
+import sys
+import time
+
+
+def get_parser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("path", type=str)
+    p.add_argument("-O", action="store_true", help="fp16 + cuda_ray + preload: what this engine always runs")
+    p.add_argument("--workspace", type=str, default="workspace")
+    p.add_argument("--seed", type=int, default=0)
+    # training options
+    p.add_argument("--iters", type=int, default=30000, help="training iters")
+    p.add_argument("--lr", type=float, default=1e-2, help="initial learning rate")
+    p.add_argument("--num_rays", type=int, default=4096, help="num rays sampled per image for each training step")
+    p.add_argument("--max_steps", type=int, default=1024, help="max num steps sampled per ray")
+    p.add_argument("--update_extra_interval", type=int, default=16, help="iter interval to update the density grid")
+    p.add_argument("--sample_budget", type=int, default=2 ** 20,
+                   help="rows of the per-step sample buffers (the fixed M): rows past a step's sample count cost "
+                        "nothing, rays past the budget are dropped for that step")
+    # dataset options
+    p.add_argument("--downscale", type=int, default=1)
+    p.add_argument("--bound", type=float, default=2,
+                   help="assume the scene is bounded in box[-bound, bound]^3, if > 1, will invoke adaptive ray marching.")
+    p.add_argument("--scale", type=float, default=0.33, help="scale camera location into box[-bound, bound]^3")
+    p.add_argument("--offset", type=float, nargs="*", default=[0, 0, 0], help="offset of camera location")
+    p.add_argument("--dt_gamma", type=float, default=1 / 128,
+                   help="dt_gamma (>=0) for adaptive ray marching. set to 0 to disable")
+    p.add_argument("--min_near", type=float, default=0.2, help="minimum near distance for camera")
+    p.add_argument("--density_thresh", type=float, default=10, help="threshold for density grid to be occupied")
+    return p
+
+
+def _eval_split(path):
+    for sp in ("val", "test"):
+        if os.path.exists(os.path.join(path, f"transforms_{sp}.json")):
+            return sp
+    return "train"  # one transforms.json: the training views themselves
+
+
+def main(argv=None):
+    opt = get_parser().parse_args(argv)
+
+    import torch
+
+    from nerf.eval import psnr
+    from nerf.fused import FusedTrainer
+    from nerf.fused_render import FusedRenderer
+    from nerf.network_ff import NeRFNetwork
+    from nerf.provider import NeRFDataset
+
+    dev = torch.device("cuda:0")
+    torch.manual_seed(opt.seed)
+    bound = int(opt.bound) if float(opt.bound).is_integer() else opt.bound
+    data_args = dict(downscale=opt.downscale, scale=opt.scale, offset=opt.offset, store="uint8")
+    train = NeRFDataset(opt.path, dev, type="train", num_rays=opt.num_rays, **data_args)
+    model = NeRFNetwork(encoding="hashgrid", bound=bound, cuda_ray=True, density_scale=1, min_near=opt.min_near,
+                        density_thresh=opt.density_thresh).to(dev)
+    model.train()
+    model.mark_untrained_grid(train.poses, train.intrinsics)
+    M = (int(opt.sample_budget) + 127) // 128 * 128
+    ft = FusedTrainer(model, train, M=M, lr=opt.lr, iters=opt.iters, max_steps=opt.max_steps,
+                      dt_gamma=opt.dt_gamma, seed=opt.seed)
+    print(f"[main_nerf] {train.images.shape[0]} images {train.H}x{train.W}x{train.images.shape[3]} "
+          f"({train.images.numel() / 2 ** 20:.0f} MiB uint8), {opt.num_rays} rays/step, sample budget {M}")
+
+    every = max(1, int(opt.update_extra_interval))
+    log_every = max(every, opt.iters // 20 // every * every)
+    over = torch.zeros((), dtype=torch.int64, device=dev)  # recorded steps whose samples passed the budget
+    checked, done, captured = 0, 0, False
+    t0 = time.perf_counter()
+    while done < opt.iters:
+        # the reference's cadence (utils.py:580-582): an update at every interval's first step
+        ft.update_density()
+        k = min(every, opt.iters - done)
+        if captured:
+            ft.run(k)
+        else:
+            for _ in range(k):  # the first interval eagerly, then the graphs
+                ft.step()
+            if k == every and done + k < opt.iters:
+                ft.capture(warmup=0, multi=max(every - 1, 1))
+                captured = True
+        done += k
+        n = min(k, 16)
+        over += ft.over_budget(n)
+        checked += n
+        if done % log_every == 0 or done == opt.iters:
+            print(f"[main_nerf] step {done}/{opt.iters} loss {ft.last_loss:.6f} "
+                  f"({time.perf_counter() - t0:.1f} s)")
+    ft.flush()
+    torch.cuda.synchronize()
+    secs = time.perf_counter() - t0
+    errors = ft.device_errors()
+    print(f"[main_nerf] trained {opt.iters} steps in {secs:.1f} s; {int(over.item())} of {checked} recorded steps "
+          f"passed the sample budget of {M} rows (their last rays were dropped); device errors {errors}")
+
+    # evaluation: the reference's eval_step over the val (or test) split
+    split = _eval_split(opt.path)
+    val = train if split == "train" else NeRFDataset(opt.path, dev, type=split, num_rays=opt.num_rays, **data_args)
+    model.eval()
+    renderer = FusedRenderer(model, val.H * val.W, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma)
+    renderer.load_weights()
+    scores = [psnr(model, val, i, dt_gamma=opt.dt_gamma, renderer=renderer) for i in range(val.poses.shape[0])]
+    finite = [s for s in scores if math.isfinite(s)]
+    mean_psnr = sum(finite) / len(finite) if finite else float("inf")
+    print(f"[main_nerf] PSNR {mean_psnr:.4f} over {len(scores)} {split} images")
+    model.train()
+
+    ckpt_dir = os.path.join(opt.workspace, "checkpoints")
+    os.makedirs(ckpt_dir, exist_ok=True)
+    ckpt = os.path.join(ckpt_dir, "ngp.pth")
+    state = ft.checkpoint()
+    state["stats"]["results"].append(mean_psnr)
+    torch.save(state, ckpt)
+    print(f"[main_nerf] checkpoint {ckpt}")
+    return {"psnr": mean_psnr, "loss": ft.last_loss, "over_budget": int(over.item()), "checkpoint": ckpt,
+            "seconds": secs}
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -242,6 +242,30 @@ class FusedTrainer:
         self._nboxes = len(LEGO_BOXES)
         self._intr = (ctypes.c_float * 4)(*[float(v) for v in dataset.intrinsics])
         self._aabb = (ctypes.c_float * 6)(*model.aabb_train.detach().cpu().tolist())
+        # An image dataset (an `images` stack, nerf.provider.NeRFDataset) is the
+        # batch source instead of the boxes: the draw gathers each ray's target
+        # from images[pose][pixel] on the device (ngp_image_source), through the
+        # image forms of the draw's entries. SyntheticLego has no images.
+        images = getattr(dataset, "images", None)
+        self._src = None
+        if images is not None:
+            n_poses, H_, W_ = int(dataset.poses.shape[0]), int(dataset.H), int(dataset.W)
+            if images.dim() != 4 or tuple(images.shape[:3]) != (n_poses, H_, W_) or images.shape[3] not in (3, 4):
+                raise ValueError(f"FusedTrainer: dataset.images must be [n_poses, H, W, 3 or 4] = "
+                                 f"[{n_poses}, {H_}, {W_}, C], got {list(images.shape)}")
+            if images.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"FusedTrainer: dataset.images must be uint8 or float32, got {images.dtype}")
+            if not images.is_contiguous():
+                raise ValueError("FusedTrainer: dataset.images must be contiguous")
+            if images.device != dev:
+                raise ValueError(f"FusedTrainer: dataset.images is on {images.device}, the model on {dev}")
+            self.pix, self.image_index = z(N, dtype=torch.int32), z(1, dtype=torch.int32)
+            src = nat.ImageSource()
+            src.pixels, src.channels = nat.ptr(images), int(images.shape[3])
+            src.dtype = nat.DTYPE_U8 if images.dtype == torch.uint8 else _F32
+            src.pix, src.image_index = nat.ptr(self.pix), nat.ptr(self.image_index)
+            self._src, self._images = src, images  # (the stack is kept alive with its pointer)
+            self._boxes, self._nboxes = None, 0
         # World 1: the grid forward reads the fp32 table and rounds each value to
         # half as it loads it (the same values autocast's cast gives), so Adam
         # does not write an fp16 copy of the table (2 of its 28 B / parameter).
@@ -282,6 +306,10 @@ class FusedTrainer:
         # occupancy image); the step head then only draws the batch.
         # march_adam=False: Adam in the head launch, before the march.
         self._march_adam = self._merge_head and opts["march_adam"]
+        if self._src is not None and self._merge_head and not self._march_adam:
+            # that step draws its batch in ngp_fused_optimizer_update_head, which has no image form
+            raise ValueError("FusedTrainer: option march_adam=False draws the batch in the Adam head launch, which "
+                             "cannot read an image dataset; keep march_adam, or set split_head=True as well")
         if self._march_adam:
             o, job = self._opt, nat.AdamJob()
             job.n_tensors = o["n"]
@@ -319,7 +347,8 @@ class FusedTrainer:
             m_, d_, bj = self.model, self.data, nat.BatchJob()
             bj.poses, bj.n_poses, bj.intrinsics4 = nat.ptr(d_.poses), d_.poses.shape[0], ctypes.addressof(self._intr)
             bj.H, bj.W, bj.N = d_.H, d_.W, self.N
-            bj.boxes, bj.nboxes, bj.aabb6 = ctypes.addressof(self._boxes), self._nboxes, ctypes.addressof(self._aabb)
+            bj.boxes = ctypes.addressof(self._boxes) if self._src is None else None
+            bj.nboxes, bj.aabb6 = self._nboxes, ctypes.addressof(self._aabb)
             bj.min_near, bj.seed, bj.state = float(m_.min_near), self.seed, nat.ptr(self.state)
             bj.rays_o, bj.rays_d, bj.rgba, bj.bg = (nat.ptr(self.rays_o), nat.ptr(self.rays_d), nat.ptr(self.rgba),
                                                     nat.ptr(self.bg))
@@ -581,6 +610,13 @@ class FusedTrainer:
         old = self.model.step_counter[(draw - 1 - k) & 15, 0].long()
         return torch.cat([old, self.counter[:1].long()])
 
+    def over_budget(self, n):
+        """How many of the last n batches (n <= 16, the step-counter ring)
+        marched more samples than the M rows of the sample buffers, so that
+        their last rays were dropped (reference raymarching.cu:416): a device
+        scalar, no host sync."""
+        return (self._recent_counts(n) > self.M).sum()
+
     def ring_times(self, last=None):
         """Per-phase device time of the last replays of the timing ring
         (`capture(ring=R)`; the events are nodes of the replayed graphs, so
@@ -792,14 +828,17 @@ class FusedTrainer:
         # the batch is drawn, so the networks are packed in _network instead
         if nets is None:
             nets = 0 if self.dp else 2
-        nat.check(lib.ngp_fused_step_head(P(d.poses), d.poses.shape[0], self._intr, d.H, d.W, self.N,
-                                          self._boxes, self._nboxes, self._aabb, float(m.min_near), self.seed,
-                                          P(self.state), P(self.rays_o), P(self.rays_d), P(self.rgba), P(self.bg),
-                                          P(self.nears), P(self.fars), P(self.noises), P(self.counter),
-                                          P(m.step_counter), 2.0, 0.5, self.growth_interval, 1, P(self.loss_ray),
-                                          nets, pk["w"], pk["ins"], pk["hid"], pk["nl"], pk["img"],
-                                          P(self.grid_ws) if self._grid_counter_bytes else None,
-                                          self._grid_counter_bytes, s),
+        # the batch source: the analytic boxes, or the dataset's image stack
+        head, source = ((lib.ngp_fused_step_head, (self._boxes, self._nboxes)) if self._src is None else
+                        (lib.ngp_fused_step_head_images, (ctypes.byref(self._src),)))
+        nat.check(head(P(d.poses), d.poses.shape[0], self._intr, d.H, d.W, self.N,
+                       *source, self._aabb, float(m.min_near), self.seed,
+                       P(self.state), P(self.rays_o), P(self.rays_d), P(self.rgba), P(self.bg),
+                       P(self.nears), P(self.fars), P(self.noises), P(self.counter),
+                       P(m.step_counter), 2.0, 0.5, self.growth_interval, 1, P(self.loss_ray),
+                       nets, pk["w"], pk["ins"], pk["hid"], pk["nl"], pk["img"],
+                       P(self.grid_ws) if self._grid_counter_bytes else None,
+                       self._grid_counter_bytes, s),
                   "fused_step_head")
         self._tick("step_head")
 
@@ -942,6 +981,18 @@ class FusedTrainer:
                                      self._inf_flag, s), "ffmlp_reduce")
             self._tick("ffmlp_reduce")
             chk(lib.ngp_grid_encode_backward_fused(*bargs, s), "grid_backward_fused")
+        elif draw and self._src is not None:
+            # + the next step's batch from the image stack (one entry for both
+            # row forms: the live rows, or every row below the sample count)
+            rows, n = (P(self._live_bufs["rows"]), P(self._live_bufs["total"])) if self._live else (None, cnt)
+            iargs = (P(self.g_enc), P(self.xyzs), float(m.bound), P(e.offsets), P(self.grads[0]), M, rows, n,
+                     *grid_args[:-1], self._offsets_host, P(self.grid_ws), self.grid_ws.numel(), self._grid_flags,
+                     self._inf_flag)
+            chk(lib.ngp_grid_encode_backward_fused_reduce_batch_images(
+                *iargs, 2, pk["ws"], pk["B"], pk["ins"], pk["hid"], pk["nl"], pk["gw"], self._inf_flag,
+                ctypes.byref(self._batch_job), ctypes.byref(self._src), s),
+                "grid_backward_fused_reduce_batch_images")
+            self._ahead = True
         elif draw and self._live:
             # over the live rows (the MLP backward wrote g_enc for those only)
             lv = self._live_bufs

@@ -189,15 +189,22 @@ class NeRFDataset:
     image centre (:419-434). sample() is the reference's collate for training
     (:442-508): num_rays random pixels of one random image, through get_rays,
     with their ground-truth colours gathered; on the GPU the same batch feeds
-    nerf.train.Trainer exactly like SyntheticLego does."""
+    nerf.train.Trainer exactly like SyntheticLego does.
+    store: how `images` [n, H, W, C] is kept on the device: "float32" (v / 255)
+    or "uint8" (the decoded bytes, a quarter of the memory; sample() and the
+    fused engine's image source divide by 255 as they gather, the same values
+    bit for bit)."""
 
-    def __init__(self, path, device, type="train", downscale=1, scale=0.33, offset=(0, 0, 0), num_rays=4096):
+    def __init__(self, path, device, type="train", downscale=1, scale=0.33, offset=(0, 0, 0), num_rays=4096,
+                 store="float32"):
         import json
         import os
 
         from PIL import Image
 
-        self.device, self.num_rays = device, num_rays
+        if store not in ("float32", "uint8"):
+            raise ValueError(f"NeRFDataset: store must be 'float32' or 'uint8', got {store!r}")
+        self.device, self.num_rays, self.store = device, num_rays, store
         if os.path.exists(os.path.join(path, "transforms.json")):
             self.mode = "colmap"
             with open(os.path.join(path, "transforms.json")) as f:
@@ -229,10 +236,14 @@ class NeRFDataset:
                 W, H = img.size[0] // downscale, img.size[1] // downscale
             if img.size != (W, H):
                 img = img.resize((W, H), Image.BOX)
-            images.append(np.asarray(img, dtype=np.float32) / 255.0)
+            images.append(np.asarray(img, dtype=np.uint8) if store == "uint8"
+                          else np.asarray(img, dtype=np.float32) / 255.0)
         self.H, self.W = H, W
         self.poses = torch.from_numpy(np.stack(poses)).to(device)
         self.images = torch.from_numpy(np.stack(images)).to(device)
+        # the uint8 store's divisor as a tensor: a true division on every device
+        # (torch multiplies by the reciprocal when a GPU tensor is divided by a number)
+        self._div = torch.full((1,), 255.0, device=device)
         if "fl_x" in transform or "fl_y" in transform:
             fl_x = (transform["fl_x"] if "fl_x" in transform else transform["fl_y"]) / downscale
             fl_y = (transform["fl_y"] if "fl_y" in transform else transform["fl_x"]) / downscale
@@ -256,5 +267,7 @@ class NeRFDataset:
         C = self.images.shape[-1]
         images = torch.gather(self.images[index:index + 1].view(1, -1, C), 1,
                               rays["inds"].unsqueeze(-1).expand(1, rays["inds"].shape[-1], C))
+        if images.dtype == torch.uint8:
+            images = images.float() / self._div
         return {"H": self.H, "W": self.W, "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "images": images,
                 "index": index}
