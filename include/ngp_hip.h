@@ -812,6 +812,49 @@ int ngp_density_grid_run_max(const float* sigma, const int32_t* indices, uint32_
 int ngp_density_mean_count(const int32_t* step_counter, const int32_t* draw, const int32_t* counter,
                            uint32_t total, uint32_t ahead, int64_t* out, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Mesh export (replaces extract_fields / extract_geometry, nerf/utils.py    */
+/* :172-202, and the PyMCubes call of Trainer.save_mesh, :688-708)           */
+/* ------------------------------------------------------------------------ */
+
+/* Conventions of the three entries: a lattice of nx x ny x nz points, index
+ * p = (i * ny + j) * nz + k (meshgrid(x, y, z, 'ij') order, utils.py:183-186);
+ * a cell is named by its minimum corner; a point is inside when value >=
+ * threshold (NaN: outside, read as 0 by the interpolation). aabb: six floats
+ * on the host, min then max. Errors are found before any device work:
+ * NGP_ERR_ARG for a resolution below 2, nx * ny * nz >= 2^31, a null
+ * required pointer, a workspace that is too small, a non-finite threshold or
+ * an aabb with max <= min; NGP_ERR_UNSUPPORTED for V or T >= 2^31. */
+
+/* The world positions of lattice points [lo, hi), xyzs f32 [hi - lo, 3]: per
+ * axis min + (max - min) * ((float)i / (float)(n - 1)) in fp32, the points
+ * extract_fields draws with torch.linspace for extract_geometry and
+ * Trainer.save_mesh (nerf/utils.py:172-202, :688-708). */
+int ngp_mesh_lattice_points(uint32_t nx, uint32_t ny, uint32_t nz, const float* aabb, uint32_t lo, uint32_t hi,
+                            float* xyzs, void* stream);
+/* Marching cubes over volume f32 [nx, ny, nz] (the mcubes.marching_cubes call
+ * of extract_geometry, nerf/utils.py:172-202, for save_mesh, :688-708), pass 1: per lattice point the crossed +x / +y /
+ * +z edges and its cell's triangle count, then their exclusive scans into
+ * the workspace (no atomics: the order below is fixed and two runs give the
+ * same bytes). counts: device uint64[2], the vertex and triangle totals V, T;
+ * the caller reads them to allocate the outputs of ngp_mesh_emit. */
+size_t ngp_mesh_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int ngp_mesh_count(const float* volume, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void* ws,
+                   size_t ws_bytes, uint64_t* counts, void* stream);
+/* Pass 2, on the workspace ngp_mesh_count filled from the same volume and
+ * threshold: vertices f32 [V, 3] ordered by (p, axis), each on the edge from p
+ * along axis at t = (threshold - a) / (b - a), a the value at p and b at the
+ * +axis neighbour, in lattice units as mcubes returns them (aabb NULL) or
+ * mapped per axis by min + (max - min) * (pos / (n - 1)) (nerf/utils.py:172-202,
+ * the mapping at :198-201; the vertices and triangles save_mesh, :688-708, exports);
+ * faces int32 [T, 3] ordered by (cell, case-table order), normals pointing
+ * from inside to outside; normals f32 [V, 3] or NULL: the normalised negative
+ * gradient of the volume (central differences, one-sided on the border). V =
+ * T = 0: nothing is launched. */
+int ngp_mesh_emit(const float* volume, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, const float* aabb,
+                  const void* ws, size_t ws_bytes, uint64_t V, uint64_t T, float* vertices, float* normals,
+                  int32_t* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

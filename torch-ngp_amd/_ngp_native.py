@@ -171,6 +171,11 @@ SIGNATURES = {
     "ngp_grid_encode_backward_fused_reduce": [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_vp, c_u32, c_u32, c_u32,
                                               c_f32, c_u32, c_u32, c_i32, c_u32, c_vp, c_vp, c_sz, c_i32, c_vp,
                                               c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_mesh_lattice_points": [c_u32, c_u32, c_u32, c_vp, c_u32, c_u32, c_vp, c_vp],
+    "ngp_mesh_workspace_bytes": [c_u32, c_u32, c_u32],
+    "ngp_mesh_count": [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_sz, c_vp, c_vp],
+    "ngp_mesh_emit": [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_vp, c_sz, ctypes.c_uint64, ctypes.c_uint64,
+                      c_vp, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {
     "ngp_last_error": ctypes.c_char_p,
@@ -190,6 +195,7 @@ _RESTYPES = {
     "ngp_density_grid_ostat_workspace_bytes": c_sz,
     "ngp_grad_exchange_bins": c_u32,
     "ngp_grad_exchange_words": ctypes.c_uint64,
+    "ngp_mesh_workspace_bytes": c_sz,
 }
 
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}

@@ -5,7 +5,10 @@ configuration (-O: fp16, cuda_ray, preloaded images), with its flag names and
 defaults, on nerf.fused.FusedTrainer: the images stay on the device as uint8
 and every batch is gathered there (the engine's image source), the steps
 between two density-grid updates replay as captured graphs, and nothing syncs
-with the host per step.
+with the host per step. --save_mesh writes the trained density field's
+triangle mesh (device marching cubes, nerf/mesh.py) to
+<workspace>/meshes/ngp.ply after the evaluation, where the reference calls
+trainer.save_mesh (main_nerf.py:190 / :241).
 
 Not here: --error_map importance sampling, patch sampling,
 --color_space linear, depth supervision, more than one image per batch."""
@@ -41,6 +44,10 @@ def get_parser():
                    help="dt_gamma (>=0) for adaptive ray marching. set to 0 to disable")
     p.add_argument("--min_near", type=float, default=0.2, help="minimum near distance for camera")
     p.add_argument("--density_thresh", type=float, default=10, help="threshold for density grid to be occupied")
+    # mesh export (the reference's trainer.save_mesh(resolution=256, threshold=10), main_nerf.py:190 / :241)
+    p.add_argument("--save_mesh", action="store_true", help="write <workspace>/meshes/ngp.ply after the evaluation")
+    p.add_argument("--mesh_resolution", type=int, default=256, help="lattice points per axis of the mesh's volume")
+    p.add_argument("--mesh_threshold", type=float, default=10, help="density at which the surface is drawn")
     return p
 
 
@@ -127,8 +134,15 @@ def main(argv=None):
     state["stats"]["results"].append(mean_psnr)
     torch.save(state, ckpt)
     print(f"[main_nerf] checkpoint {ckpt}")
-    return {"psnr": mean_psnr, "loss": ft.last_loss, "over_budget": int(over.item()), "checkpoint": ckpt,
-            "seconds": secs}
+    result = {"psnr": mean_psnr, "loss": ft.last_loss, "over_budget": int(over.item()), "checkpoint": ckpt,
+              "seconds": secs}
+    if opt.save_mesh:
+        ft.workspace = opt.workspace
+        path, nv, nt = ft.save_mesh(resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)
+        print(f"[main_nerf] mesh {path}: {nv} vertices, {nt} triangles "
+              f"(resolution {opt.mesh_resolution}, threshold {opt.mesh_threshold:g})")
+        result.update(mesh=path, mesh_vertices=nv, mesh_triangles=nt)
+    return result
 
 
 if __name__ == "__main__":

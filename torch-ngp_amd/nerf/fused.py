@@ -31,6 +31,7 @@ scan/emit are both memory-bound and slowed each other more than they
 overlapped (profiles/r01u_overlap_trace.txt).
 """
 import ctypes
+import os
 import sys
 
 import numpy as np
@@ -114,6 +115,7 @@ class FusedTrainer:
         assert enc.level_dim == 2 and enc.num_levels * enc.level_dim == 32 and enc.input_dim == 3
         assert model.sigma_net.input_dim == 32 and model.color_net.input_dim == 32
         self.model, self.data = model, dataset
+        self.workspace = None  # set by the caller that has one: save_mesh's default directory
         dev = model.density_bitfield.device
         self.dev = dev
         self.N = N = int(dataset.num_rays)
@@ -1162,6 +1164,20 @@ class FusedTrainer:
         # (a skipped update is never silent)
         if self._xchg is not None and self._xchg.check():
             self._recapture()
+
+    def save_mesh(self, path=None, resolution=256, threshold=10):
+        """Trainer.save_mesh (nerf/utils.py:688-708): the pending update is
+        applied first, then nerf.mesh.save_mesh writes the density field's mesh
+        over aabb_infer as a binary PLY. path None: <workspace>/meshes/ngp.ply
+        when `workspace` is set. -> (path, vertex count, triangle count)."""
+        from . import mesh
+        if path is None:
+            if not self.workspace:
+                raise RuntimeError("FusedTrainer.save_mesh: a path is needed (the trainer has no workspace)")
+            path = os.path.join(self.workspace, "meshes", "ngp.ply")
+        self.flush()
+        nv, nt = mesh.save_mesh(self.model, path, resolution=resolution, threshold=threshold)
+        return path, nv, nt
 
     def capture(self, warmup=2, ring=0, multi=1):
         """hipGraph(s) of the step body. World 1: one graph (optimizer of the
