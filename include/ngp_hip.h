@@ -458,13 +458,23 @@ int ngp_grid_encode_backward_fused_reduce_batch_live(
  *   pix (nullable) i32 [N]: each ray's flat pixel index j * W + i (the
  *     reference's results['inds'], nerf/utils.py:112);
  *   image_index (nullable) i32 [1]: the draw's image.
- * Bad channels / dtype / null pixels: NGP_ERR_ARG before any device work. */
+ *   depths (nullable) f32 [n_poses, H, W]: a depth map per image (the
+ *     reference's dep_path maps, nerf/provider.py:346-357, 555-557). Ray n then
+ *     also gets depth_out[n] = depths[pose][pix] * depth_scale (one fp32
+ *     multiply: file units -> ngp units), from the pose and pixel its colour
+ *     comes from. Null (a zeroed tail): colours only, as before these fields.
+ *   depth_out f32 [N]: required with depths.
+ * Bad channels / dtype / null pixels, depths without depth_out: NGP_ERR_ARG
+ * before any device work. */
 typedef struct ngp_image_source {
     const void* pixels;
     uint32_t channels;
     int32_t dtype;
     int32_t* pix;
     int32_t* image_index;
+    const float* depths;
+    float depth_scale;
+    float* depth_out;
 } ngp_image_source;
 /* ngp_lego_rays with the image source in place of the boxes. */
 int ngp_image_rays(const float* poses, uint32_t n_poses, const float* intrinsics4, uint32_t H, uint32_t W,
@@ -617,6 +627,38 @@ int ngp_nerf_composite_loss_live(const float* sigma, const void* color_out, cons
                                  void* state, void* grad_color_out, void* grad_h_sigma, float* out_image,
                                  float* out_ws, float* loss_ray, int32_t* ray_rows, int32_t* live_cnt,
                                  int32_t* live_rows, int32_t* live_total, void* stream);
+/* The depth-supervised loss (the reference's train_step, nerf/utils.py:545-553
+ * and :951-954): per ray, with pred the composite's own depth (0 for a ray
+ * without samples or dropped for overflowing M),
+ *   mask = depth_min <= gt && gt <= depth_max     (model.min_near, model.bound)
+ *   dep  = mask ? |gt - max(pred, 0)| : 0
+ *   loss_ray[n] = color_weight * mse + depth_weight * dep
+ * The colour gradients are scaled by color_weight, and the depth gradient
+ * scale * depth_weight / N * sign(pred - gt) (0 outside the mask, sign(0) = 0)
+ * reaches the densities through the composite backward (raymarching.cu:674).
+ * dep is a select where the reference multiplies by the mask: a masked ray
+ * (a NaN or inf target too) contributes exactly +0 here.
+ *   gt_depth f32 [N] by ray index, ngp units (nullable with depth_weight 0:
+ *     every ray masked); out_depth (nullable) f32 [N] by ray index: pred;
+ *   loss_depth_ray (nullable) f32 [N], ray n's unweighted dep;
+ *   ray_rows / live_cnt / live_rows / live_total: all four as
+ *     ngp_nerf_composite_loss_live lists the live rows, or all four null. */
+typedef struct ngp_depth_loss_job {
+    const float* gt_depth;
+    float color_weight, depth_weight;
+    float depth_min, depth_max;
+    float* out_depth;
+    float* loss_depth_ray;
+    int32_t *ray_rows, *live_cnt, *live_rows, *live_total;
+} ngp_depth_loss_job;
+/* ngp_nerf_composite_loss (live lists null) / ngp_nerf_composite_loss_live with
+ * the job's loss. color_weight 1 and depth_weight 0 give those entries' outputs
+ * bit for bit. */
+int ngp_nerf_composite_loss_depth(const float* sigma, const void* color_out, const void* h_sigma,
+                                  const float* deltas, const int32_t* rays, uint32_t M, uint32_t N, float T_thresh,
+                                  float density_scale, const float* gt, uint32_t gt_channels, const float* bg,
+                                  void* state, void* grad_color_out, void* grad_h_sigma, float* out_image,
+                                  float* out_ws, float* loss_ray, const ngp_depth_loss_job* job, void* stream);
 /* scaler_enabled of the optimizer entries: GradScaler off; on, with its inf
  * check as a sweep over the grads; on, with the check already made by the
  * kernels that wrote the grads into the state's flag (ngp_fused_inf_flag). */

@@ -146,6 +146,8 @@ SIGNATURES = {
     "ngp_nerf_composite_loss_live": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
                                      c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                      c_vp],
+    "ngp_nerf_composite_loss_depth": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
+                                      c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_fused_optimizer_step": [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32,
                                  c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_i32, c_u32, c_vp, c_vp,
                                  c_vp, c_vp, c_vp],
@@ -228,8 +230,18 @@ class BatchJob(ctypes.Structure):
 
 class ImageSource(ctypes.Structure):
     """ngp_image_source (include/ngp_hip.h): the pixel stack the fused step's
-    batch takes its targets from, and the draw's pixel / image indices."""
-    _fields_ = [("pixels", c_vp), ("channels", c_u32), ("dtype", c_i32), ("pix", c_vp), ("image_index", c_vp)]
+    batch takes its targets from, and the draw's pixel / image indices; with
+    a depth stack, each ray's depths[pose][pix] * depth_scale into depth_out."""
+    _fields_ = [("pixels", c_vp), ("channels", c_u32), ("dtype", c_i32), ("pix", c_vp), ("image_index", c_vp),
+                ("depths", c_vp), ("depth_scale", c_f32), ("depth_out", c_vp)]
+
+
+class DepthLossJob(ctypes.Structure):
+    """ngp_depth_loss_job (include/ngp_hip.h): the depth term and the loss
+    weights of ngp_nerf_composite_loss_depth, and its optional live-row lists."""
+    _fields_ = [("gt_depth", c_vp), ("color_weight", c_f32), ("depth_weight", c_f32), ("depth_min", c_f32),
+                ("depth_max", c_f32), ("out_depth", c_vp), ("loss_depth_ray", c_vp), ("ray_rows", c_vp),
+                ("live_cnt", c_vp), ("live_rows", c_vp), ("live_total", c_vp)]
 
 
 _lib = None

@@ -14,7 +14,9 @@
 //   k_composite_loss  per ray (one wave, shuffle scans): composite forward,
 //                     background blend, MSE, d loss / d image (AMP-scaled),
 //                     composite backward, cast/sigmoid/trunc_exp backward ->
-//                     fp16 MLP-output grads
+//                     fp16 MLP-output grads; <true>: plus the masked L1
+//                     depth term and the colour / depth loss weights
+//                     (ngp_nerf_composite_loss_depth, utils.py:545-553, 951-954)
 //   k_glue_bwd        geo-feature grads (color MLP grad_inputs 16..30) -> h1..15
 //   k_nonfinite       GradScaler's inf/nan check over the fp16 grads
 //   k_adam_multi      Adam over all parameter tensors, unscaled fp16 grads,
@@ -120,6 +122,15 @@ struct LossArgs {
     uint32_t gt_channels;                         // 4: RGBA with random background, 3: RGB on white
 };
 
+// The depth term of the loss (ngp_depth_loss_job; k_composite_loss<true> only):
+// loss = cw * mse + dw * (lo <= gt && gt <= hi ? |gt - max(depth, 0)| : 0).
+struct DepthArgs {
+    const float* gt;  // [N] by ray index, ngp units; null: every ray masked
+    float cw, dw, lo, hi;
+    float* out_depth;       // nullable [N] by ray index: the composite's depth
+    float* loss_depth_ray;  // nullable [N]: ray n's unweighted depth term
+};
+
 // One 64-sample chunk of a ray: per-lane sample data and the scanned quantities.
 struct Chunk {
     bool ok, active;                 // lane holds a sample / sample is before the early stop
@@ -189,6 +200,9 @@ NGP_DEV Chunk scan_chunk(const Raw& rw, uint32_t base, uint32_t num_steps, uint3
 // forward and 3 more in the backward).
 constexpr uint32_t kLossPre = 4;
 
+// kDepth: the depth-supervised loss (DepthArgs); false is the colour-only
+// kernel, which reads nothing of `da`.
+template <bool kDepth>
 __global__ void __launch_bounds__(kLossWaves * 64)
 k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ color_out,
                  const ngp_half* __restrict__ h_sigma, const float* __restrict__ deltas,
@@ -197,7 +211,7 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
                  StepState* __restrict__ st, ngp_half* __restrict__ grad_color_out,
                  ngp_half* __restrict__ grad_h, float* __restrict__ out_image,
                  float* __restrict__ out_ws, float* __restrict__ loss_ray, int32_t* __restrict__ ray_rows,
-                 int32_t* __restrict__ live_cnt) {
+                 int32_t* __restrict__ live_cnt, DepthArgs da) {
     typedef _Float16 half8 __attribute__((ext_vector_type(8)));
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * kLossWaves + (threadIdx.x >> 6);
@@ -217,6 +231,11 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
     for (int k = 0; k < 4; ++k) {
         const float v = gt[(size_t)index * gch + min((uint32_t)k, gch - 1u)];
         gt4[k] = (uint32_t)k < gch ? v : 1.0f;
+    }
+    // (depth loss: the ray's target depth, one more 4-byte load in the same round trip)
+    float gtd = 0.0f;
+    if constexpr (kDepth) {
+        if (da.gt) gtd = da.gt[index];
     }
     // the ray's first kLossPre chunks of rows (clamped: a short ray's spare
     // chunks read its row 0 again)
@@ -275,19 +294,39 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
         q0 = gt4[0]; q1 = gt4[1]; q2 = gt4[2];
     }
     const float e0 = p0 - q0, e1 = p1 - q1, e2 = p2 - q2;
+    // depth term (utils.py:545-553): masked L1 between the target and the
+    // composite's depth clamped at 0 (renderer.py:369); a select, so a masked
+    // ray (NaN / inf targets too) contributes exactly +0. d is 0 for a ray
+    // without samples or dropped for overflowing M.
+    float gd = 0.0f;  // d loss / d depth (AMP-scaled); colour-only: depth is not in the loss
+    float cw = 1.0f;
+    if constexpr (kDepth) {
+        cw = da.cw;
+        const bool mask = da.gt != nullptr && da.lo <= gtd && gtd <= da.hi;
+        const float pd = fmaxf(d, 0.0f);
+        const float dep = mask ? fabsf(gtd - pd) : 0.0f;
+        // (loss * scale).backward(): dw -> mean -> abs -> clamp (passes d >= 0)
+        const float sgn = pd > gtd ? 1.0f : (pd < gtd ? -1.0f : 0.0f);
+        if (mask && d >= 0.0f) gd = ((st->scale * da.dw) * la.inv_n) * sgn;
+        if (lane == 0) {
+            loss_ray[n] = da.cw * (((e0 * e0 + e1 * e1) + e2 * e2) * la.inv_c) + da.dw * dep;
+            if (da.out_depth) da.out_depth[index] = d;
+            if (da.loss_depth_ray) da.loss_depth_ray[n] = dep;
+        }
+    }
     if (lane == 0) {
         // per-ray loss; summed by k_step_end (one reduction, no contended atomics)
-        loss_ray[n] = ((e0 * e0 + e1 * e1) + e2 * e2) * la.inv_c;
+        if constexpr (!kDepth) loss_ray[n] = ((e0 * e0 + e1 * e1) + e2 * e2) * la.inv_c;
         if (out_image) {
             out_image[index * 3] = p0; out_image[index * 3 + 1] = p1; out_image[index * 3 + 2] = p2;
         }
         if (out_ws) out_ws[index] = ws;
     }
     // (loss * scale).backward(): mean -> mean(-1) -> pow(2) -> sub
-    const float G = (st->scale * la.inv_n) * la.inv_c;
+    // (depth loss: the colour term's weight first, cw * loss_rgb; cw = 1 changes no bit)
+    const float G = ((kDepth ? st->scale * cw : st->scale) * la.inv_n) * la.inv_c;
     const float gr = G * (2.0f * e0), gg = G * (2.0f * e1), gb = G * (2.0f * e2);
     const float gws = -((gr * bg0 + gg * bg1) + gb * bg2);  // d/dws of image + (1 - ws) * bg
-    const float gd = 0.0f;                                  // depth is not in the loss
 
     // ---- backward (composite_rays_train_backward) + activation backward
     if (!valid) {
@@ -696,10 +735,10 @@ extern "C" int ngp_nerf_composite_loss(const float* sigma, const void* color_out
     la.inv_n = 1.0f / (float)N;
     la.inv_c = 1.0f / 3.0f;
     la.gt_channels = gt_channels;
-    k_composite_loss<<<ngp_div_up(N, kLossWaves), kLossWaves * 64, 0, ngp_stream(stream)>>>(
+    k_composite_loss<false><<<ngp_div_up(N, kLossWaves), kLossWaves * 64, 0, ngp_stream(stream)>>>(
         sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
         static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
-        out_ws, loss_ray, nullptr, nullptr);
+        out_ws, loss_ray, nullptr, nullptr, DepthArgs{});
     return ngp_check_launch("nerf_composite_loss");
 }
 
@@ -728,13 +767,54 @@ extern "C" int ngp_nerf_composite_loss_live(const float* sigma, const void* colo
     la.inv_n = 1.0f / (float)N;
     la.inv_c = 1.0f / 3.0f;
     la.gt_channels = gt_channels;
-    k_composite_loss<<<ngp_div_up(N, kLossWaves), kLossWaves * 64, 0, st>>>(
+    k_composite_loss<false><<<ngp_div_up(N, kLossWaves), kLossWaves * 64, 0, st>>>(
         sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
         static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
-        out_ws, loss_ray, ray_rows, live_cnt);
+        out_ws, loss_ray, ray_rows, live_cnt, DepthArgs{});
     k_live_compact<<<ngp_div_up(N, kLiveRaysPerBlock), kLiveThreads, 0, st>>>(rays, live_cnt, ray_rows, N, live_rows,
                                                                               live_total);
     return ngp_check_launch("nerf_composite_loss_live");
+}
+
+extern "C" int ngp_nerf_composite_loss_depth(const float* sigma, const void* color_out, const void* h_sigma,
+                                             const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                             float T_thresh, float density_scale, const float* gt,
+                                             uint32_t gt_channels, const float* bg, void* state,
+                                             void* grad_color_out, void* grad_h_sigma, float* out_image,
+                                             float* out_ws, float* loss_ray, const ngp_depth_loss_job* job,
+                                             void* stream) {
+    NGP_REQUIRE(job, NGP_ERR_ARG, "composite_loss_depth: null job");
+    NGP_REQUIRE(loss_ray, NGP_ERR_ARG, "composite_loss_depth: loss_ray [N] buffer required");
+    NGP_REQUIRE(gt_channels == 3 || gt_channels == 4, NGP_ERR_ARG, "composite_loss_depth: gt must be RGB or RGBA");
+    NGP_REQUIRE(job->gt_depth || job->depth_weight == 0.0f, NGP_ERR_ARG,
+                "composite_loss_depth: a depth weight needs the gt_depth [N] buffer");
+    const bool live = job->ray_rows || job->live_cnt || job->live_rows || job->live_total;
+    NGP_REQUIRE(!live || (job->ray_rows && job->live_cnt && job->live_rows && job->live_total), NGP_ERR_ARG,
+                "composite_loss_depth: ray_rows [M] / live_cnt [N] / live_rows [M] / live_total: all or none");
+    NGP_REQUIRE(!live || (reinterpret_cast<uintptr_t>(job->live_cnt) & 15) == 0, NGP_ERR_ARG,
+                "composite_loss_depth: live_cnt must be 16-byte aligned");
+    hipStream_t st = ngp_stream(stream);
+    if (N == 0) {
+        if (live && hipMemsetAsync(job->live_total, 0, sizeof(int32_t), st) != hipSuccess)
+            return ngp_set_error(NGP_ERR_HIP, "composite_loss_depth: memset failed");
+        return NGP_OK;
+    }
+    LossArgs la;
+    la.T_thresh = T_thresh;
+    la.density_scale = density_scale;
+    la.inv_n = 1.0f / (float)N;
+    la.inv_c = 1.0f / 3.0f;
+    la.gt_channels = gt_channels;
+    const DepthArgs da{job->gt_depth, job->color_weight, job->depth_weight, job->depth_min, job->depth_max,
+                       job->out_depth, job->loss_depth_ray};
+    k_composite_loss<true><<<ngp_div_up(N, kLossWaves), kLossWaves * 64, 0, st>>>(
+        sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
+        static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
+        out_ws, loss_ray, job->ray_rows, job->live_cnt, da);
+    if (live)
+        k_live_compact<<<ngp_div_up(N, kLiveRaysPerBlock), kLiveThreads, 0, st>>>(rays, job->live_cnt, job->ray_rows,
+                                                                                  N, job->live_rows, job->live_total);
+    return ngp_check_launch("nerf_composite_loss_depth");
 }
 
 extern "C" int ngp_fused_optimizer_step(int32_t n_tensors, float* const* params, void* const* grads,

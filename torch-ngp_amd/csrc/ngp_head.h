@@ -43,6 +43,10 @@ struct LegoScene {
     const void* pixels;
     uint32_t channels;
     int32_t pix_dtype;
+    // ... and its depth stack [n_poses, H, W] float32 (null: colours only),
+    // gathered as depths[pose][pix] * depth_scale
+    const float* depths;
+    float depth_scale;
 };
 
 // near/far against the aabb, reference raymarching.cu:91-145 (same as
@@ -76,6 +80,8 @@ struct LegoOut {
     // image source only, nullable: each ray's flat pixel index j * W + i (the
     // reference's results['inds'], utils.py:112) and the draw's image
     int32_t *pix, *image_index;
+    // image source with a depth stack: each ray's target depth [N]
+    float* depth;
 };
 
 static inline LegoScene make_scene(uint32_t n_poses, const float* intrinsics4, uint32_t H, uint32_t W,
@@ -110,6 +116,7 @@ static inline int check_image_source(const ngp_image_source* src, const char* wh
     const uintptr_t align = src->dtype == NGP_DTYPE_F32 ? (src->channels == 4 ? 16 : 4) : (src->channels == 4 ? 4 : 1);
     NGP_REQUIRE((reinterpret_cast<uintptr_t>(src->pixels) & (align - 1)) == 0, NGP_ERR_ARG,
                 "%s: pixels must be %u-byte aligned", who, (unsigned)align);
+    NGP_REQUIRE(!src->depths || src->depth_out, NGP_ERR_ARG, "%s: a depth stack needs the depth_out [N] buffer", who);
     return NGP_OK;
 }
 // A checked source into the scene and the draw's outputs.
@@ -120,6 +127,9 @@ static inline void set_image_source(LegoScene& sc, LegoOut& out, const ngp_image
     sc.pix_dtype = src->dtype;
     out.pix = src->pix;
     out.image_index = src->image_index;
+    sc.depths = src->depths;
+    sc.depth_scale = src->depth_scale;
+    out.depth = src->depths ? src->depth_out : nullptr;
 }
 
 // The image source's target of pixel `pix` of image `pose`: RGBA as stored
@@ -152,6 +162,8 @@ NGP_DEV bool image_target(uint32_t n, uint32_t pose, uint32_t pix, const LegoSce
     out.rgba[n * 4 + 1] = g;
     out.rgba[n * 4 + 2] = b;
     out.rgba[n * 4 + 3] = a;
+    // the depth map's value of the same pixel, file units -> ngp units (uniform across the launch)
+    if (sc.depths) out.depth[n] = sc.depths[px] * sc.depth_scale;
     if (out.pix) out.pix[n] = (int32_t)pix;
     if (out.image_index && n == 0) out.image_index[0] = (int32_t)pose;
     if (sc.channels == 4) return false;

@@ -8,10 +8,13 @@ between two density-grid updates replay as captured graphs, and nothing syncs
 with the host per step. --save_mesh writes the trained density field's
 triangle mesh (device marching cubes, nerf/mesh.py) to
 <workspace>/meshes/ngp.ply after the evaluation, where the reference calls
-trainer.save_mesh (main_nerf.py:190 / :241).
+trainer.save_mesh (main_nerf.py:190 / :241). --depth_loss_weight > 0 adds the
+reference's depth supervision on scenes whose frames carry a dep_path: the
+loss is color_loss_weight * rgb + depth_loss_weight * dep (nerf/utils.py
+:545-553, 951-954), the depths gathered on the device beside the colours.
 
 Not here: --error_map importance sampling, patch sampling,
---color_space linear, depth supervision, more than one image per batch."""
+--color_space linear, more than one image per batch."""
 import argparse
 import math
 import os
@@ -34,12 +37,18 @@ def get_parser():
     p.add_argument("--sample_budget", type=int, default=2 ** 20,
                    help="rows of the per-step sample buffers (the fixed M): rows past a step's sample count cost "
                         "nothing, rays past the budget are dropped for that step")
+    # loss weights (the reference's opt.color_loss_weight / opt.depth_loss_weight)
+    p.add_argument("--depth_loss_weight", type=float, default=0.0,
+                   help="weight of the masked L1 depth loss (needs a dep_path per frame)")
+    p.add_argument("--color_loss_weight", type=float, default=1.0, help="weight of the colour MSE")
     # dataset options
     p.add_argument("--downscale", type=int, default=1)
     p.add_argument("--bound", type=float, default=2,
                    help="assume the scene is bounded in box[-bound, bound]^3, if > 1, will invoke adaptive ray marching.")
     p.add_argument("--scale", type=float, default=0.33, help="scale camera location into box[-bound, bound]^3")
     p.add_argument("--offset", type=float, nargs="*", default=[0, 0, 0], help="offset of camera location")
+    p.add_argument("--depth_scale", type=float, default=None,
+                   help="depth-map units to scene units, gt = depth * depth_scale (default: --scale)")
     p.add_argument("--dt_gamma", type=float, default=1 / 128,
                    help="dt_gamma (>=0) for adaptive ray marching. set to 0 to disable")
     p.add_argument("--min_near", type=float, default=0.2, help="minimum near distance for camera")
@@ -63,7 +72,7 @@ def main(argv=None):
 
     import torch
 
-    from nerf.eval import psnr
+    from nerf.eval import depth_error, psnr
     from nerf.fused import FusedTrainer
     from nerf.fused_render import FusedRenderer
     from nerf.network_ff import NeRFNetwork
@@ -72,15 +81,20 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     torch.manual_seed(opt.seed)
     bound = int(opt.bound) if float(opt.bound).is_integer() else opt.bound
-    data_args = dict(downscale=opt.downscale, scale=opt.scale, offset=opt.offset, store="uint8")
+    data_args = dict(downscale=opt.downscale, scale=opt.scale, offset=opt.offset, store="uint8",
+                     depth_scale=opt.depth_scale)
     train = NeRFDataset(opt.path, dev, type="train", num_rays=opt.num_rays, **data_args)
     model = NeRFNetwork(encoding="hashgrid", bound=bound, cuda_ray=True, density_scale=1, min_near=opt.min_near,
                         density_thresh=opt.density_thresh).to(dev)
     model.train()
     model.mark_untrained_grid(train.poses, train.intrinsics)
     M = (int(opt.sample_budget) + 127) // 128 * 128
-    ft = FusedTrainer(model, train, M=M, lr=opt.lr, iters=opt.iters, max_steps=opt.max_steps,
-                      dt_gamma=opt.dt_gamma, seed=opt.seed)
+    try:
+        ft = FusedTrainer(model, train, M=M, lr=opt.lr, iters=opt.iters, max_steps=opt.max_steps,
+                          dt_gamma=opt.dt_gamma, seed=opt.seed, depth_loss_weight=opt.depth_loss_weight,
+                          color_loss_weight=opt.color_loss_weight)
+    except ValueError as e:  # e.g. a depth weight on a scene without depth maps
+        sys.exit(f"[main_nerf] {e}")
     print(f"[main_nerf] {train.images.shape[0]} images {train.H}x{train.W}x{train.images.shape[3]} "
           f"({train.images.numel() / 2 ** 20:.0f} MiB uint8), {opt.num_rays} rays/step, sample budget {M}")
 
@@ -106,7 +120,9 @@ def main(argv=None):
         over += ft.over_budget(n)
         checked += n
         if done % log_every == 0 or done == opt.iters:
-            print(f"[main_nerf] step {done}/{opt.iters} loss {ft.last_loss:.6f} "
+            dep = ft.last_depth_loss  # None: the colour-only loss
+            terms = "" if dep is None else f" (rgb {ft.last_color_loss:.6f}, dep {dep:.6f})"
+            print(f"[main_nerf] step {done}/{opt.iters} loss {ft.last_loss:.6f}{terms} "
                   f"({time.perf_counter() - t0:.1f} s)")
     ft.flush()
     torch.cuda.synchronize()
@@ -125,6 +141,14 @@ def main(argv=None):
     finite = [s for s in scores if math.isfinite(s)]
     mean_psnr = sum(finite) / len(finite) if finite else float("inf")
     print(f"[main_nerf] PSNR {mean_psnr:.4f} over {len(scores)} {split} images")
+    # ... and the supervised depth term over the same views, when the split has depth maps
+    mean_depth = None
+    if val.depths is not None:
+        errs = [depth_error(model, val, i, dt_gamma=opt.dt_gamma, max_steps=opt.max_steps)
+                for i in range(val.poses.shape[0])]
+        errs = [e for e in errs if math.isfinite(e)]
+        mean_depth = sum(errs) / len(errs) if errs else float("nan")
+        print(f"[main_nerf] depth error {mean_depth:.6f} over {val.poses.shape[0]} {split} images")
     model.train()
 
     ckpt_dir = os.path.join(opt.workspace, "checkpoints")
@@ -135,7 +159,7 @@ def main(argv=None):
     torch.save(state, ckpt)
     print(f"[main_nerf] checkpoint {ckpt}")
     result = {"psnr": mean_psnr, "loss": ft.last_loss, "over_budget": int(over.item()), "checkpoint": ckpt,
-              "seconds": secs}
+              "seconds": secs, "depth_error": mean_depth}
     if opt.save_mesh:
         ft.workspace = opt.workspace
         path, nv, nt = ft.save_mesh(resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)

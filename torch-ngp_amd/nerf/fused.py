@@ -12,6 +12,11 @@ glue fused into the hot-path kernels (DESIGN.md "fused step"):
     -> color FFMLP backward -> glue backward -> sigma FFMLP backward
     -> grid_encode backward(fused) -> GradScaler check + Adam + update
 
+With loss weights other than the defaults (depth_loss_weight > 0 or
+color_loss_weight != 1) the draws also gather each ray's depth from the
+dataset's depth maps and the composite runs its depth form
+(ngp_nerf_composite_loss_depth); the launches are the same.
+
 Static shapes: N rays per step, M = the sample buffer (mean_count); rows past
 the marcher's sample count are skipped on the device, so a fixed M costs
 nothing beyond its memory. Every launch goes to the current stream, so the
@@ -94,7 +99,8 @@ DEFAULT_OPTIONS = dict(table16=False, split_head=False, split_reduce=False, spli
 class FusedTrainer:
     def __init__(self, model, dataset, M, lr=1e-2, iters=30000, max_steps=1024, T_thresh=1e-4,
                  dt_gamma=0.0, seed=0, betas=(0.9, 0.99), eps=1e-15, init_scale=65536.0,
-                 growth_interval=2000, distributed=False, grid_timing=False, options=None):
+                 growth_interval=2000, distributed=False, grid_timing=False, options=None,
+                 depth_loss_weight=0.0, color_loss_weight=1.0):
         """distributed: ray-sharded data parallelism over the initialised
         torch.distributed group: each rank draws its own rays; the flat fp16
         gradient is averaged with one RCCL reduce-scatter, each rank's Adam
@@ -103,7 +109,15 @@ class FusedTrainer:
         grid_timing: the binned grid backward times itself on the chip's
         constant clock (`grid_timing()`, the bench's roofline clock); off by
         default, since it adds ring stores to the backward's launches.
-        options: DEFAULT_OPTIONS overrides (the step's structure)."""
+        options: DEFAULT_OPTIONS overrides (the step's structure).
+        depth_loss_weight, color_loss_weight: the reference's pixel loss
+        color_loss_weight * rgb + depth_loss_weight * dep (nerf/utils.py:951-954),
+        dep the masked L1 between the composite's depth and the dataset's depth
+        maps (`dataset.depths`, :545-553). With the defaults (0, 1) the step is
+        the colour-only one, launch for launch; otherwise the draws gather each
+        ray's depth beside its colour and the composite runs its depth form
+        (ngp_nerf_composite_loss_depth). Data parallel: the same launches on
+        every rank (the loss is a per-rank mean, the gradients are averaged)."""
         opts = dict(DEFAULT_OPTIONS)
         for k, v in (options or {}).items():
             if k not in opts:
@@ -123,6 +137,15 @@ class FusedTrainer:
         self.max_steps, self.T_thresh, self.dt_gamma = int(max_steps), float(T_thresh), float(dt_gamma)
         self.lr, self.iters, self.betas, self.eps = float(lr), int(iters), betas, float(eps)
         self.growth_interval, self.seed = int(growth_interval), int(seed)
+        self.depth_loss_weight, self.color_loss_weight = float(depth_loss_weight), float(color_loss_weight)
+        if self.depth_loss_weight < 0 or self.color_loss_weight < 0:
+            raise ValueError("FusedTrainer: the loss weights must not be negative")
+        # the depth form of the draw and of the composite, only where the loss differs from the colour-only one
+        self._depth = self.depth_loss_weight > 0 or self.color_loss_weight != 1
+        depths = getattr(dataset, "depths", None)
+        if self.depth_loss_weight > 0 and depths is None:
+            raise ValueError("FusedTrainer: depth_loss_weight > 0 needs a dataset with depth maps (dataset.depths: "
+                             "a dep_path per frame, nerf.provider.NeRFDataset); this one has none")
         self.density_seed = int(seed)  # the density-grid draws are the same on every rank
         # dp: the data-parallel (ZeRO-1) step with its collectives, also at
         # world size 1 (a one-rank group runs the same RCCL calls);
@@ -268,6 +291,29 @@ class FusedTrainer:
             src.pix, src.image_index = nat.ptr(self.pix), nat.ptr(self.image_index)
             self._src, self._images = src, images  # (the stack is kept alive with its pointer)
             self._boxes, self._nboxes = None, 0
+        # depth supervision: the draws gather depths[pose][pix] * depth_scale into
+        # gt_depth beside the colours, and the composite compares its depth to it
+        self._loss_job = None
+        if self._depth:
+            self.gt_depth, self.out_depth, self.loss_depth_ray = z(N), z(N), z(N)
+            if self.depth_loss_weight > 0:
+                if self._src is None:
+                    raise ValueError("FusedTrainer: depth_loss_weight > 0 needs an image dataset (dataset.images)")
+                want = (int(dataset.poses.shape[0]), int(dataset.H), int(dataset.W))
+                if tuple(depths.shape) != want or depths.dtype != torch.float32 or not depths.is_contiguous():
+                    raise ValueError(f"FusedTrainer: dataset.depths must be contiguous float32 [n_poses, H, W] = "
+                                     f"{list(want)}, got {depths.dtype} {list(depths.shape)}")
+                if depths.device != dev:
+                    raise ValueError(f"FusedTrainer: dataset.depths is on {depths.device}, the model on {dev}")
+                self._src.depths, self._src.depth_scale = nat.ptr(depths), float(dataset.depth_scale)
+                self._src.depth_out = nat.ptr(self.gt_depth)
+                self._depths = depths
+            lj = nat.DepthLossJob()
+            lj.gt_depth = nat.ptr(self.gt_depth) if self.depth_loss_weight > 0 else None
+            lj.color_weight, lj.depth_weight = self.color_loss_weight, self.depth_loss_weight
+            lj.depth_min, lj.depth_max = float(model.min_near), float(model.bound)
+            lj.out_depth, lj.loss_depth_ray = nat.ptr(self.out_depth), nat.ptr(self.loss_depth_ray)
+            self._loss_job = lj
         # World 1: the grid forward reads the fp32 table and rounds each value to
         # half as it loads it (the same values autocast's cast gives), so Adam
         # does not write an fp16 copy of the table (2 of its 28 B / parameter).
@@ -368,6 +414,12 @@ class FusedTrainer:
             i32 = torch.int32
             self._live_bufs = dict(ray_rows=z(M, dtype=i32), cnt=z(N, dtype=i32), rows=z(M, dtype=i32),
                                    total=z(4, dtype=i32))
+        if self._loss_job is not None and self._live:
+            # (a batch's composite runs its live form exactly when it draws ahead: see _network)
+            lb, lj = self._live_bufs, self._loss_job
+            self._loss_job_live = lj_live = nat.DepthLossJob.from_buffer_copy(lj)
+            lj_live.ray_rows, lj_live.live_cnt = nat.ptr(lb["ray_rows"]), nat.ptr(lb["cnt"])
+            lj_live.live_rows, lj_live.live_total = nat.ptr(lb["rows"]), nat.ptr(lb["total"])
         self.graph = None
         self.graph_multi, self._multi = None, 1  # capture(multi=S): S step bodies in one graph
         # data parallel over RCCL: the whole step is captured, collectives included
@@ -924,6 +976,15 @@ class FusedTrainer:
         live = self._live and draw
         if live:
             lv = self._live_bufs
+        if self._loss_job is not None:
+            # the depth-supervised loss (and its weights): one entry for both row forms
+            job = self._loss_job_live if live else self._loss_job
+            chk(lib.ngp_nerf_composite_loss_depth(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
+                                                  P(self.rays), M, N, self.T_thresh, float(m.density_scale),
+                                                  P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
+                                                  P(self.g_h), None, None, P(self.loss_ray), ctypes.byref(job), s),
+                "composite_loss_depth")
+        elif live:
             chk(lib.ngp_nerf_composite_loss_live(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                                  P(self.rays), M, N, self.T_thresh, float(m.density_scale),
                                                  P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
@@ -1359,6 +1420,27 @@ class FusedTrainer:
     def last_loss(self):
         self.flush()
         return float(self._state_f()[2].item())
+
+    @property
+    def last_depth_loss(self):
+        """The last step's unweighted depth term, the mean over its rays of the
+        masked |gt - depth| (`last_loss` is the weighted total); None when the
+        step runs the colour-only loss."""
+        if self._loss_job is None:
+            return None
+        self.flush()
+        return float(self.loss_depth_ray.mean().item())
+
+    @property
+    def last_color_loss(self):
+        """The last step's unweighted colour term (the MSE), from the weighted
+        total and the depth term; None for the colour-only loss (`last_loss` is
+        it), nan when color_loss_weight is 0."""
+        if self._loss_job is None:
+            return None
+        if self.color_loss_weight == 0:
+            return float("nan")
+        return (self.last_loss - self.depth_loss_weight * self.last_depth_loss) / self.color_loss_weight
 
     @property
     def scale(self):

@@ -193,10 +193,18 @@ class NeRFDataset:
     store: how `images` [n, H, W, C] is kept on the device: "float32" (v / 255)
     or "uint8" (the decoded bytes, a quarter of the memory; sample() and the
     fused engine's image source divide by 255 as they gather, the same values
-    bit for bit)."""
+    bit for bit).
+    Depth maps (the reference's dep_path, :346-357, 390-391): a frame's
+    `dep_path` names an .npz whose `depth` is [H, W] or [H, W, 1]; the maps are
+    stacked into `depths` [n, H, W] float32 on the device, in file units,
+    nearest-resized with the images (cv2.INTER_NEAREST's rule: source index
+    floor(i * src / dst)). Every frame has one or none has (`depths` None).
+    depth_scale: file units -> ngp units, gt = depth * depth_scale (default: the
+    pose `scale`; the reference's 2 * bound / aabb_size is the caller's to
+    pass); sample() returns "depths" [1, N] in ngp units (:555-557)."""
 
     def __init__(self, path, device, type="train", downscale=1, scale=0.33, offset=(0, 0, 0), num_rays=4096,
-                 store="float32"):
+                 store="float32", depth_scale=None):
         import json
         import os
 
@@ -224,7 +232,7 @@ class NeRFDataset:
         H = W = None
         if "h" in transform and "w" in transform:
             H, W = int(transform["h"]) // downscale, int(transform["w"]) // downscale
-        poses, images = [], []
+        poses, images, depths, no_depth = [], [], [], None
         for fr in frames:
             fp = os.path.join(path, fr["file_path"])
             if self.mode == "blender" and "." not in os.path.basename(fp):
@@ -238,7 +246,29 @@ class NeRFDataset:
                 img = img.resize((W, H), Image.BOX)
             images.append(np.asarray(img, dtype=np.uint8) if store == "uint8"
                           else np.asarray(img, dtype=np.float32) / 255.0)
+            if "dep_path" in fr:
+                with np.load(os.path.join(path, fr["dep_path"])) as f:
+                    depth = np.asarray(f["depth"], dtype=np.float32)
+                if depth.ndim == 3 and depth.shape[-1] == 1:
+                    depth = depth[..., 0]
+                if depth.ndim != 2:
+                    raise ValueError(f"NeRFDataset: {fr['dep_path']}: depth must be [H, W] or [H, W, 1], "
+                                     f"got {list(depth.shape)}")
+                if depth.shape != (H, W):
+                    rows = np.minimum(np.floor(np.arange(H) * (depth.shape[0] / H)).astype(np.int64),
+                                      depth.shape[0] - 1)
+                    cols = np.minimum(np.floor(np.arange(W) * (depth.shape[1] / W)).astype(np.int64),
+                                      depth.shape[1] - 1)
+                    depth = depth[rows][:, cols]
+                depths.append(depth)
+            elif no_depth is None:
+                no_depth = fr["file_path"]
+        if depths and no_depth is not None:
+            raise ValueError(f"NeRFDataset: frame {no_depth!r} has no dep_path, but other frames have one "
+                             "(depth maps for every frame, or for none)")
         self.H, self.W = H, W
+        self.depths = torch.from_numpy(np.ascontiguousarray(np.stack(depths))).to(device) if depths else None
+        self.depth_scale = float(scale if depth_scale is None else depth_scale)
         self.poses = torch.from_numpy(np.stack(poses)).to(device)
         self.images = torch.from_numpy(np.stack(images)).to(device)
         # the uint8 store's divisor as a tensor: a true division on every device
@@ -269,5 +299,9 @@ class NeRFDataset:
                               rays["inds"].unsqueeze(-1).expand(1, rays["inds"].shape[-1], C))
         if images.dtype == torch.uint8:
             images = images.float() / self._div
-        return {"H": self.H, "W": self.W, "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "images": images,
-                "index": index}
+        out = {"H": self.H, "W": self.W, "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "images": images,
+               "index": index}
+        if self.depths is not None:
+            # the same pixels' depths, in ngp units (one fp32 multiply, as the fused engine's gather)
+            out["depths"] = torch.gather(self.depths[index:index + 1].view(1, -1), 1, rays["inds"]) * self.depth_scale
+        return out

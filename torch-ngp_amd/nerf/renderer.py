@@ -191,6 +191,8 @@ class NeRFRenderer(nn.Module):
             weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays,
                                                                          T_thresh)
             image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
+            # the composite's depth in ngp units, what depth supervision compares (renderer.py:369)
+            results["depth_bound_scale"] = torch.clamp(depth, min=0).view(*prefix)
             depth = torch.clamp(depth - nears, min=0) / (fars - nears)
             results["weights_sum"] = weights_sum
             image = image.view(*prefix, 3)

@@ -39,12 +39,19 @@ def average_gradients(params, group=None):
 class Trainer:
     def __init__(self, model, dataset, lr=1e-2, iters=30000, fp16=True, dt_gamma=0.0,
                  max_steps=1024, update_extra_interval=16, update_density=True,
-                 distributed=False):
+                 distributed=False, depth_loss_weight=0.0, color_loss_weight=1.0, perturb=True):
+        """depth_loss_weight, color_loss_weight: the reference's pixel loss
+        color_loss_weight * rgb + depth_loss_weight * dep (nerf/utils.py:951-954)
+        on batches that carry "depths" (:545-553). perturb: the march's jitter
+        (off for comparisons on a fixed batch)."""
         self.model = model
         self.dataset = dataset
         self.fp16 = fp16
         self.dt_gamma = dt_gamma
         self.max_steps = max_steps
+        self.depth_loss_weight, self.color_loss_weight = float(depth_loss_weight), float(color_loss_weight)
+        self.perturb = bool(perturb)
+        self.last_depth_loss = None
         self.update_extra_interval = update_extra_interval
         self.update_density = update_density
         self.distributed = distributed and dist.is_available() and dist.is_initialized()
@@ -71,10 +78,19 @@ class Trainer:
         with torch.autocast("cuda", dtype=torch.float16, enabled=self.fp16,
                             cache_enabled=self.graph is None and self.static is None):
             outputs = self.model.render(data["rays_o"], data["rays_d"], staged=False,
-                                        bg_color=bg_color, perturb=True, force_all_rays=False,
+                                        bg_color=bg_color, perturb=self.perturb, force_all_rays=False,
                                         dt_gamma=self.dt_gamma, max_steps=self.max_steps)
             pred_rgb = outputs["image"]
             loss = ((pred_rgb - gt_rgb) ** 2).mean(-1).mean()
+            if "depths" in data:
+                # the reference's masked L1 on the composite's depth (utils.py:545-553), both in ngp units
+                gt_dep, pred_dep = data["depths"], outputs["depth_bound_scale"]
+                mask = (self.model.min_near <= gt_dep) & (gt_dep <= self.model.bound)
+                dep = (torch.abs(gt_dep - pred_dep) * mask.float()).mean()
+                self.last_depth_loss = dep.detach()
+                loss = self.color_loss_weight * loss + self.depth_loss_weight * dep
+            elif self.color_loss_weight != 1:
+                loss = self.color_loss_weight * loss
         self.scaler.scale(loss).backward()
         return loss
 
