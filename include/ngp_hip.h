@@ -464,8 +464,32 @@ int ngp_grid_encode_backward_fused_reduce_batch_live(
  *     multiply: file units -> ngp units), from the pose and pixel its colour
  *     comes from. Null (a zeroed tail): colours only, as before these fields.
  *   depth_out f32 [N]: required with depths.
- * Bad channels / dtype / null pixels, depths without depth_out: NGP_ERR_ARG
- * before any device work. */
+ *   error_map (nullable) f32 [n_poses, res * res]: the reference's --error_map
+ *     (nerf/provider.py:397-401, nerf/utils.py:101-113): a coarse res x res
+ *     error image per pose, cell = row_cell * res + col_cell, finite and >= 0.
+ *     The draw's pixels then come from the N cells ngp_error_map_select chose
+ *     for this draw (`selected`, ascending), not from stream 1's uniform pixel:
+ *       r    = rng_u32(seed, it, 0xffffffff, 1) % N
+ *       cell = selected[((uint64)n * perm_mult + r) % N]
+ *       sx = (float)H / res, sy = (float)W / res           (fp32, no contraction)
+ *       row = min((uint32)((float)(cell / res) * sx + rng_unit(seed, it, n, 7) * sx), H - 1)
+ *       col = min((uint32)((float)(cell % res) * sy + rng_unit(seed, it, n, 8) * sy), W - 1)
+ *       pix = row * W + col, coarse[n] = cell
+ *     and everything else of ray n (direction from pix, target and depth
+ *     gather, background, noise, near/far, counters) is unchanged. Null (a
+ *     zeroed tail): the uniform draw, bit for bit as before these fields.
+ *   error_map_res: 1..128 with a map.
+ *   selected i32 [N]: ngp_error_map_select's output for this draw; the select
+ *     is issued on the same stream just before the launch that draws.
+ *   perm_mult: in [1, N], coprime to N, so that n -> (n * perm_mult + r) % N
+ *     is a permutation (the caller's: the largest such integer <= 0.618 N
+ *     spreads the ascending cells over the ray indices).
+ *   coarse i32 [N] by ray index: the reference's inds_coarse, read back by
+ *     ngp_error_map_update. Required with a map.
+ * Bad channels / dtype / null pixels, depths without depth_out, a map without
+ * selected / coarse or with a res outside 1..128, N > res * res or a
+ * perm_mult that is no permutation of N, map fields without a map:
+ * NGP_ERR_ARG before any device work. */
 typedef struct ngp_image_source {
     const void* pixels;
     uint32_t channels;
@@ -475,7 +499,43 @@ typedef struct ngp_image_source {
     const float* depths;
     float depth_scale;
     float* depth_out;
+    const float* error_map;
+    uint32_t error_map_res;
+    const int32_t* selected;
+    uint32_t perm_mult;
+    int32_t* coarse;
 } ngp_image_source;
+/* Weighted draw without replacement of N of the res * res cells of one row of
+ * the error map, torch.multinomial(w, N, replacement=False)'s exponential race
+ * on the counter RNG (nerf/utils.py:104): with it = state->draw (the draw the
+ * next batch launch makes) and pose = rng_u32(seed, it, 0xffffffff, 0) % n_poses,
+ * cell c of row `pose` (weight w) gets
+ *   k = rng_u32(seed, it, c, 6) >> 8,  u = (float)(k + 1) * 2^-24  in (0, 1]
+ *   key = w > 0 ? w / -logf(u) : 0           (u = 1: +inf)
+ * and the N largest keys win, ties (the all-zero map too) to the lower cell.
+ * selected[N]: the winners in ascending cell order, the same bytes on every
+ * run. keys_out (nullable) f32 [res * res]: every cell's key. One workgroup;
+ * nothing is read back to the host, so the launch replays in a graph.
+ * Null map / selected / state, n_poses 0, res outside 1..128, N == 0 or
+ * N > res * res: NGP_ERR_ARG before any device work. */
+int ngp_error_map_select(const float* error_map, uint32_t n_poses, uint32_t res, uint32_t N, uint32_t seed,
+                         const void* state, int32_t* selected, float* keys_out, void* stream);
+/* The EMA the reference folds each ray's loss into the map with
+ * (nerf/utils.py:578-600): for every ray n of the batch (rays without samples
+ * or dropped past the sample budget too), with index = rays[n * 3],
+ *   err = ((e0^2 + e1^2) + e2^2) * (1/3)f    the composite's per-ray colour term:
+ *         e = out_image[index] - blend(gt[index], bg[index]), as
+ *         ngp_nerf_composite_loss computes its loss_ray, whatever the weights
+ *   map[image_index[0]][coarse[index]] = 0.1f * old + 0.9f * err
+ * One deviation from the reference: a non-finite or negative err leaves the
+ * cell as it was, so the map stays finite and >= 0 (the select relies on it).
+ * out_image f32 [N, 3] by ray index is the composite's output of this batch;
+ * gt f32 [N, gt_channels] and bg f32 [N, 3] are its targets. Cells are unique
+ * within a batch (no race). Null buffers, n_poses 0, res outside 1..128,
+ * N > res * res: NGP_ERR_ARG before any device work. */
+int ngp_error_map_update(float* error_map, uint32_t n_poses, uint32_t res, uint32_t N, const int32_t* rays,
+                         const float* out_image, const float* gt, uint32_t gt_channels, const float* bg,
+                         const int32_t* image_index, const int32_t* coarse, void* stream);
 /* ngp_lego_rays with the image source in place of the boxes. */
 int ngp_image_rays(const float* poses, uint32_t n_poses, const float* intrinsics4, uint32_t H, uint32_t W,
                    uint32_t N, const ngp_image_source* src, const float* aabb6, float min_near, uint32_t seed,

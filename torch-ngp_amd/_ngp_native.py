@@ -132,6 +132,8 @@ SIGNATURES = {
                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_image_rays": [c_vp, c_u32, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_f32, c_u32,
                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_error_map_select": [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
+    "ngp_error_map_update": [c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp],
     "ngp_fused_step_head_images": [c_vp, c_u32, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_f32, c_u32, c_vp,
                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_i32, c_i32,
                                    c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp],
@@ -231,9 +233,13 @@ class BatchJob(ctypes.Structure):
 class ImageSource(ctypes.Structure):
     """ngp_image_source (include/ngp_hip.h): the pixel stack the fused step's
     batch takes its targets from, and the draw's pixel / image indices; with
-    a depth stack, each ray's depths[pose][pix] * depth_scale into depth_out."""
+    a depth stack, each ray's depths[pose][pix] * depth_scale into depth_out;
+    with an error map, the draw's pixels come from ngp_error_map_select's
+    `selected` cells and each ray's cell goes to `coarse`."""
     _fields_ = [("pixels", c_vp), ("channels", c_u32), ("dtype", c_i32), ("pix", c_vp), ("image_index", c_vp),
-                ("depths", c_vp), ("depth_scale", c_f32), ("depth_out", c_vp)]
+                ("depths", c_vp), ("depth_scale", c_f32), ("depth_out", c_vp),
+                ("error_map", c_vp), ("error_map_res", c_u32), ("selected", c_vp), ("perm_mult", c_u32),
+                ("coarse", c_vp)]
 
 
 class DepthLossJob(ctypes.Structure):

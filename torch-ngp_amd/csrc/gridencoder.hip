@@ -2911,6 +2911,9 @@ extern "C" int ngp_grid_encode_backward_fused_reduce_batch_images(
     void* const* grad_weights, int32_t* mlp_nonfinite, const ngp_batch_job* job, const ngp_image_source* src,
     void* stream) {
     if (int e = ngp_head::check_image_source(src, "grid_encode_backward_fused_reduce_batch_images")) return e;
+    if (job)
+        if (int e = ngp_head::check_error_map_draw(src, job->N, "grid_encode_backward_fused_reduce_batch_images"))
+            return e;
     NGP_REQUIRE(!job || (!job->boxes && job->nboxes == 0), NGP_ERR_ARG,
                 "grid_encode_backward_fused_reduce_batch_images: an image job carries no boxes");
     return reduce_batch_impl(grad, xyz, bound, offsets, grad_embeddings, B, live_count, D, C, L, S, H, gridtype,

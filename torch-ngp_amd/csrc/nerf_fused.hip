@@ -17,6 +17,9 @@
 //                     fp16 MLP-output grads; <true>: plus the masked L1
 //                     depth term and the colour / depth loss weights
 //                     (ngp_nerf_composite_loss_depth, utils.py:545-553, 951-954)
+//   k_error_map_select / k_error_map_update   the reference's --error_map: a
+//                     weighted draw without replacement of the batch's map
+//                     cells, and the EMA of each ray's colour error into them
 //   k_glue_bwd        geo-feature grads (color MLP grad_inputs 16..30) -> h1..15
 //   k_nonfinite       GradScaler's inf/nan check over the fp16 grads
 //   k_adam_multi      Adam over all parameter tensors, unscaled fp16 grads,
@@ -495,6 +498,155 @@ k_live_compact(const int32_t* __restrict__ rays, const int32_t* __restrict__ liv
     }
 }
 
+// ---- error-map importance sampling (the reference's --error_map) ----------------
+// The draw's N cells: torch.multinomial(w, N, replacement=False) is an
+// exponential race (cell c's key w_c / e_c, e_c ~ Exp(1); the N largest keys
+// win), restated on the counter RNG (stream 6). One workgroup; thread t keeps
+// the keys of cells [16 t, 16 t + 16) in registers (128 x 128 cells at most).
+// The keys are non-negative floats, so their bits order as unsigned integers:
+// an MSB-first radix select (8 bits a pass over a 256-bin LDS histogram) finds
+// the N-th largest key T and how many of the cells with key == T are admitted
+// (the lowest cell indices first: the tie rule); two block prefix sums in cell
+// order then rank the winners, so `selected` comes out ascending and is the
+// same on every run. Slots past the map's cells hold key 0 with the highest
+// indices, so they lose every tie (N <= res * res). No global atomics.
+// The histogram is kept in 16 copies, lane l adding to copy l & 15 (stride 257
+// words: a digit's copies lie in 16 different banks): neighbouring keys share
+// their leading bytes, and 64 lanes adding to one LDS word are served one at a
+// time (19.7 us a launch on a trained 128 x 128 map against 21.0 us with one
+// copy; most of the time is the keys' arithmetic).
+constexpr uint32_t kSelThreads = 1024, kSelPer = 16, kSelCopies = 16, kSelStride = 257;
+static_assert(kSelThreads * kSelPer == kMaxMapRes * kMaxMapRes, "one register slot per cell of the largest map");
+
+// exclusive prefix of v over the workgroup's threads (wsum: one slot per wave)
+NGP_DEV uint32_t block_scan_excl(uint32_t v, uint32_t* wsum) {
+    const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t incl = ngp_dpp::scan_incl_u32(v);
+    __syncthreads();  // (wsum may still be read from the previous scan)
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    for (uint32_t k = 0; k < wv; ++k) before += wsum[k];
+    return before + incl - v;
+}
+
+__global__ void __launch_bounds__(kSelThreads)
+k_error_map_select(const float* __restrict__ map, uint32_t n_poses, uint32_t res, uint32_t N, uint32_t seed,
+                   const StepState* __restrict__ st, int32_t* __restrict__ selected, float* __restrict__ keys_out) {
+    __shared__ uint32_t hist[kSelCopies * kSelStride];
+    __shared__ uint32_t wsum[kSelThreads / 64];
+    __shared__ uint32_t pick[2];
+    const uint32_t t = threadIdx.x, C = res * res;
+    // the draw the next batch launch makes, and its image (lego_ray's pose)
+    const uint32_t it = (uint32_t)st->draw;
+    const uint32_t pose = rng_u32(seed, it, 0xffffffffu, 0) % n_poses;
+    const float* __restrict__ w = map + (size_t)pose * C;
+    uint32_t key[kSelPer];
+#pragma unroll
+    for (uint32_t j = 0; j < kSelPer; ++j) {
+        const uint32_t c = t * kSelPer + j;
+        float kf = 0.0f;
+        if (c < C) {
+            const float wc = w[c];
+            const uint32_t k = rng_u32(seed, it, c, 6) >> 8;
+            const float u = (float)(k + 1u) * (1.0f / 16777216.0f);  // (0, 1]
+            const float e = 0.0f - logf(u);                          // Exp(1); u = 1: +0, the key +inf
+            kf = wc > 0.0f ? wc / e : 0.0f;
+            if (keys_out) keys_out[c] = kf;
+        }
+        key[j] = __builtin_bit_cast(uint32_t, kf);
+    }
+    // radix select: after the passes `prefix` is the N-th largest key and
+    // `need` the number of cells with that key among the winners
+    uint32_t prefix = 0, mask = 0, need = N;
+#pragma unroll
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (uint32_t i = t; i < kSelCopies * kSelStride; i += kSelThreads) hist[i] = 0;
+        __syncthreads();
+        uint32_t* __restrict__ mine = hist + (t & (kSelCopies - 1u)) * kSelStride;
+        // (a thread's run of equal digits is one LDS add: neighbouring cells'
+        // keys mostly share their leading bytes)
+        uint32_t run_d = 0xffffffffu, run_n = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kSelPer; ++j) {
+            if ((key[j] & mask) != prefix) continue;
+            const uint32_t dg = (key[j] >> shift) & 255u;
+            if (dg != run_d) {
+                if (run_n) atomicAdd(&mine[run_d], run_n);
+                run_d = dg;
+                run_n = 0;
+            }
+            ++run_n;
+        }
+        if (run_n) atomicAdd(&mine[run_d], run_n);
+        __syncthreads();
+        // threads 0..255 (four whole waves): thread t holds digit 255 - t, so the
+        // prefix over the threads counts the candidates with a larger digit
+        uint32_t h = 0;
+        if (t < 256) {
+#pragma unroll
+            for (uint32_t c = 0; c < kSelCopies; ++c) h += hist[c * kSelStride + 255u - t];
+        }
+        const uint32_t above = block_scan_excl(h, wsum);
+        if (t < 256 && above < need && need <= above + h) {
+            pick[0] = 255u - t;
+            pick[1] = need - above;
+        }
+        __syncthreads();
+        prefix |= pick[0] << shift;
+        mask |= 255u << shift;
+        need = pick[1];
+    }
+    // ties in cell order: the first `need` cells with key == prefix are in
+    uint32_t n_eq = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kSelPer; ++j) n_eq += key[j] == prefix;
+    uint32_t tie = block_scan_excl(n_eq, wsum);
+    uint32_t in = 0;  // bit j: cell 16 t + j is selected
+#pragma unroll
+    for (uint32_t j = 0; j < kSelPer; ++j) {
+        if (key[j] > prefix || (key[j] == prefix && tie++ < need)) in |= 1u << j;
+    }
+    uint32_t pos = block_scan_excl((uint32_t)__popc(in), wsum);
+#pragma unroll
+    for (uint32_t j = 0; j < kSelPer; ++j)
+        if ((in >> j & 1u) && pos < N) selected[pos++] = (int32_t)(t * kSelPer + j);
+}
+
+// The map's EMA of each ray's colour error (utils.py:578-600), one thread per
+// ray: e is recomputed from the composite's out_image and the targets with
+// k_composite_loss's own operations, so err equals its colour loss bit for bit.
+__global__ void __launch_bounds__(256)
+k_error_map_update(float* __restrict__ map, uint32_t n_poses, uint32_t res, uint32_t N,
+                   const int32_t* __restrict__ rays, const float* __restrict__ out_image,
+                   const float* __restrict__ gt, uint32_t gch, const float* __restrict__ bg,
+                   const int32_t* __restrict__ image_index, const int32_t* __restrict__ coarse) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3];
+    const uint32_t pose = (uint32_t)image_index[0];
+    if (index >= N || pose >= n_poses) return;
+    const uint32_t cell = (uint32_t)coarse[index];
+    if (cell >= res * res) return;
+    const float bg0 = bg[index * 3], bg1 = bg[index * 3 + 1], bg2 = bg[index * 3 + 2];
+    const float p0 = out_image[index * 3], p1 = out_image[index * 3 + 1], p2 = out_image[index * 3 + 2];
+    const float* g = gt + (size_t)index * gch;
+    float q0 = g[0], q1 = g[1], q2 = g[2];
+    if (gch == 4) {
+        const float a = g[3], om = 1.0f - a;
+        q0 = q0 * a + bg0 * om;
+        q1 = q1 * a + bg1 * om;
+        q2 = q2 * a + bg2 * om;
+    }
+    const float e0 = p0 - q0, e1 = p1 - q1, e2 = p2 - q2;
+    const float err = ((e0 * e0 + e1 * e1) + e2 * e2) * (1.0f / 3.0f);
+    // a select, not the reference's plain EMA: a non-finite or negative error
+    // leaves the cell as it was (the map stays finite and >= 0 for the select)
+    if (!(err >= 0.0f) || !__builtin_isfinite(err)) return;
+    float* cellp = map + (size_t)pose * (res * res) + cell;
+    *cellp = 0.1f * *cellp + 0.9f * err;
+}
+
 // GradScaler._unscale_grads_ inf/nan check over every grad (8 halves / lane)
 __global__ void __launch_bounds__(256)
 k_nonfinite(TensorList tl, StepState* __restrict__ st) {
@@ -692,6 +844,7 @@ extern "C" int ngp_image_rays(const float* poses, uint32_t n_poses, const float*
                               float* rgba, float* bg, float* nears, float* fars, float* noises, int32_t* counter,
                               int32_t* step_counter, void* stream) {
     if (int e = check_image_source(src, "image_rays")) return e;
+    if (int e = check_error_map_draw(src, N, "image_rays")) return e;
     NGP_REQUIRE(n_poses > 0 && H > 0 && W > 0, NGP_ERR_ARG, "image_rays: empty pose set or image");
     LegoScene sc = make_scene(n_poses, intrinsics4, H, W, nullptr, 0, aabb6, min_near, seed);
     LegoOut out{rays_o, rays_d, rgba, bg, nears, fars, noises, counter, step_counter};
@@ -700,6 +853,39 @@ extern "C" int ngp_image_rays(const float* poses, uint32_t n_poses, const float*
     k_lego_rays<<<ngp_div_up(N, 256), 256, 0, ngp_stream(stream)>>>(poses, sc, N, static_cast<StepState*>(state),
                                                                      out);
     return ngp_check_launch("image_rays");
+}
+
+extern "C" int ngp_error_map_select(const float* error_map, uint32_t n_poses, uint32_t res, uint32_t N,
+                                    uint32_t seed, const void* state, int32_t* selected, float* keys_out,
+                                    void* stream) {
+    NGP_REQUIRE(error_map && selected && state, NGP_ERR_ARG, "error_map_select: null map, selected [N] or state");
+    NGP_REQUIRE(n_poses > 0, NGP_ERR_ARG, "error_map_select: empty pose set");
+    NGP_REQUIRE(res >= 1 && res <= kMaxMapRes, NGP_ERR_ARG, "error_map_select: resolution %u (1..%u)", res,
+                kMaxMapRes);
+    NGP_REQUIRE(N >= 1 && N <= res * res, NGP_ERR_ARG,
+                "error_map_select: %u of %u x %u cells (1..res * res, drawn without replacement)", N, res, res);
+    k_error_map_select<<<1, kSelThreads, 0, ngp_stream(stream)>>>(error_map, n_poses, res, N, seed,
+                                                                  static_cast<const StepState*>(state), selected,
+                                                                  keys_out);
+    return ngp_check_launch("error_map_select");
+}
+
+extern "C" int ngp_error_map_update(float* error_map, uint32_t n_poses, uint32_t res, uint32_t N,
+                                    const int32_t* rays, const float* out_image, const float* gt,
+                                    uint32_t gt_channels, const float* bg, const int32_t* image_index,
+                                    const int32_t* coarse, void* stream) {
+    NGP_REQUIRE(error_map && rays && out_image && gt && bg && image_index && coarse, NGP_ERR_ARG,
+                "error_map_update: null map, rays, out_image, gt, bg, image_index or coarse");
+    NGP_REQUIRE(n_poses > 0, NGP_ERR_ARG, "error_map_update: empty pose set");
+    NGP_REQUIRE(gt_channels == 3 || gt_channels == 4, NGP_ERR_ARG, "error_map_update: gt must be RGB or RGBA");
+    NGP_REQUIRE(res >= 1 && res <= kMaxMapRes, NGP_ERR_ARG, "error_map_update: resolution %u (1..%u)", res,
+                kMaxMapRes);
+    NGP_REQUIRE(N <= res * res, NGP_ERR_ARG, "error_map_update: %u rays on %u x %u cells", N, res, res);
+    if (N == 0) return NGP_OK;
+    k_error_map_update<<<ngp_div_up(N, 256), 256, 0, ngp_stream(stream)>>>(error_map, n_poses, res, N, rays,
+                                                                           out_image, gt, gt_channels, bg,
+                                                                           image_index, coarse);
+    return ngp_check_launch("error_map_update");
 }
 
 extern "C" int ngp_nerf_glue_forward(const void* h_sigma, const float* dirs, float density_scale,
@@ -901,6 +1087,7 @@ extern "C" int ngp_fused_step_head_images(const float* poses, uint32_t n_poses, 
                                           const uint32_t* num_layers, void* const* images, void* clear,
                                           uint32_t clear_bytes, void* stream) {
     if (int e = check_image_source(src, "step_head_images")) return e;
+    if (int e = check_error_map_draw(src, N, "step_head_images")) return e;
     return step_head_launch(poses, n_poses, intrinsics4, H, W, N, nullptr, 0, src, aabb6, min_near, seed, state,
                             rays_o, rays_d, rgba, bg, nears, fars, noises, counter, step_counter, growth_factor,
                             backoff_factor, growth_interval, scaler_enabled, loss_ray, n_nets, mlp_weights, in_dims,

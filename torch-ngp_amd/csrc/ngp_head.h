@@ -15,6 +15,7 @@ using ngp_step::StepState;
 
 constexpr int kMaxBoxes = 8;
 constexpr int kMaxTensors = 8;
+constexpr uint32_t kMaxMapRes = 128;  // error map: at most 128 x 128 cells (the reference's size)
 
 // counter-based RNG (no state, graph-safe): 32-bit mix of (seed, a, b, c)
 NGP_DEV uint32_t mix32(uint32_t x) {
@@ -47,6 +48,11 @@ struct LegoScene {
     // gathered as depths[pose][pix] * depth_scale
     const float* depths;
     float depth_scale;
+    // ... and its error map (null: uniform pixels): the draw's pixels come from
+    // the N cells of the res x res map that ngp_error_map_select chose
+    // (`selected`, ascending), ray n taking rank (n * perm_mult + r) % N
+    const int32_t* selected;
+    uint32_t map_res, perm_mult;
 };
 
 // near/far against the aabb, reference raymarching.cu:91-145 (same as
@@ -82,6 +88,8 @@ struct LegoOut {
     int32_t *pix, *image_index;
     // image source with a depth stack: each ray's target depth [N]
     float* depth;
+    // image source with an error map: each ray's map cell [N] (the reference's inds_coarse)
+    int32_t* coarse;
 };
 
 static inline LegoScene make_scene(uint32_t n_poses, const float* intrinsics4, uint32_t H, uint32_t W,
@@ -117,6 +125,28 @@ static inline int check_image_source(const ngp_image_source* src, const char* wh
     NGP_REQUIRE((reinterpret_cast<uintptr_t>(src->pixels) & (align - 1)) == 0, NGP_ERR_ARG,
                 "%s: pixels must be %u-byte aligned", who, (unsigned)align);
     NGP_REQUIRE(!src->depths || src->depth_out, NGP_ERR_ARG, "%s: a depth stack needs the depth_out [N] buffer", who);
+    if (!src->error_map) {
+        NGP_REQUIRE(!src->selected && !src->coarse && src->error_map_res == 0 && src->perm_mult == 0, NGP_ERR_ARG,
+                    "%s: error-map fields (res, selected, perm_mult, coarse) without an error map", who);
+        return NGP_OK;
+    }
+    NGP_REQUIRE(src->error_map_res >= 1 && src->error_map_res <= kMaxMapRes, NGP_ERR_ARG,
+                "%s: error map resolution %u (1..%u)", who, src->error_map_res, kMaxMapRes);
+    NGP_REQUIRE(src->selected && src->coarse, NGP_ERR_ARG,
+                "%s: an error map needs the selected [N] and coarse [N] buffers", who);
+    return NGP_OK;
+}
+// ... and the checks that need the batch size: N cells are drawn without
+// replacement, and ray n -> rank (n * perm_mult + r) % N must be a permutation.
+static inline int check_error_map_draw(const ngp_image_source* src, uint32_t N, const char* who) {
+    if (!src->error_map || N == 0) return NGP_OK;
+    NGP_REQUIRE(N <= src->error_map_res * src->error_map_res, NGP_ERR_ARG,
+                "%s: %u rays from an error map of %u x %u cells (drawn without replacement)", who, N,
+                src->error_map_res, src->error_map_res);
+    uint32_t a = src->perm_mult, b = N;
+    while (b) { const uint32_t t = a % b; a = b; b = t; }
+    NGP_REQUIRE(src->perm_mult >= 1 && src->perm_mult <= N && a == 1, NGP_ERR_ARG,
+                "%s: perm_mult %u must be in [1, N] and coprime to N = %u", who, src->perm_mult, N);
     return NGP_OK;
 }
 // A checked source into the scene and the draw's outputs.
@@ -130,6 +160,10 @@ static inline void set_image_source(LegoScene& sc, LegoOut& out, const ngp_image
     sc.depths = src->depths;
     sc.depth_scale = src->depth_scale;
     out.depth = src->depths ? src->depth_out : nullptr;
+    sc.selected = src->error_map ? src->selected : nullptr;
+    sc.map_res = src->error_map_res;
+    sc.perm_mult = src->perm_mult;
+    out.coarse = src->error_map ? src->coarse : nullptr;
 }
 
 // The image source's target of pixel `pix` of image `pose`: RGBA as stored
@@ -175,11 +209,28 @@ NGP_DEV bool image_target(uint32_t n, uint32_t pose, uint32_t pix, const LegoSce
 // Ray n of draw `it` (the fused sampler, reference get_rays utils.py:52-136 +
 // the analytic target + background + march noise + near/far): writes the
 // ray's outputs and returns its origin / direction / near / far / noise.
-NGP_DEV void lego_ray(uint32_t n, uint32_t it, const float* __restrict__ poses, const LegoScene& sc,
+NGP_DEV void lego_ray(uint32_t n, uint32_t N, uint32_t it, const float* __restrict__ poses, const LegoScene& sc,
                       const LegoOut& out, float (&o)[3], float (&d)[3], float& nr, float& fr, float& noise) {
     const uint32_t pose = rng_u32(sc.seed, it, 0xffffffffu, 0) % sc.n_poses;
     const float* P = poses + (size_t)pose * 16;
-    const uint32_t pix = rng_u32(sc.seed, it, n, 1) % (sc.H * sc.W);
+    uint32_t pix;
+    if (sc.selected) {
+        // error map (uniform across the launch; utils.py:101-113): the cell of
+        // this ray's rank among the draw's selected cells, then a random pixel
+        // of the cell's footprint
+        const uint32_t r = rng_u32(sc.seed, it, 0xffffffffu, 1) % N;
+        const uint32_t rank = (uint32_t)(((uint64_t)n * sc.perm_mult + r) % N);
+        const uint32_t cell = min((uint32_t)sc.selected[rank], sc.map_res * sc.map_res - 1u);
+        const float sx = (float)sc.H / (float)sc.map_res, sy = (float)sc.W / (float)sc.map_res;
+        const uint32_t row = min((uint32_t)((float)(cell / sc.map_res) * sx + rng_unit(sc.seed, it, n, 7) * sx),
+                                 sc.H - 1u);
+        const uint32_t col = min((uint32_t)((float)(cell % sc.map_res) * sy + rng_unit(sc.seed, it, n, 8) * sy),
+                                 sc.W - 1u);
+        pix = row * sc.W + col;
+        out.coarse[n] = (int32_t)cell;
+    } else {
+        pix = rng_u32(sc.seed, it, n, 1) % (sc.H * sc.W);
+    }
     // get_rays (utils.py:52-136): pixel centre, camera direction, normalise, rotate
     const float i = (float)(pix % sc.W) + 0.5f;
     const float j = (float)(pix / sc.W) + 0.5f;
@@ -266,7 +317,7 @@ NGP_DEV void lego_rays_block(uint32_t blk, uint32_t nblk, const float* __restric
     lego_end(it, nblk, st);
     if (n >= N) return;
     float o[3], d[3], nr, fr, noise;
-    lego_ray(n, it, poses, sc, out, o, d, nr, fr, noise);
+    lego_ray(n, N, it, poses, sc, out, o, d, nr, fr, noise);
 }
 
 // ---- optimizer ------------------------------------------------------------------

@@ -12,9 +12,13 @@ trainer.save_mesh (main_nerf.py:190 / :241). --depth_loss_weight > 0 adds the
 reference's depth supervision on scenes whose frames carry a dep_path: the
 loss is color_loss_weight * rgb + depth_loss_weight * dep (nerf/utils.py
 :545-553, 951-954), the depths gathered on the device beside the colours.
+--error_map is the reference's importance sampling (nerf/utils.py:101-113,
+578-600): a coarse error image per training view (--error_map_res cells a
+side, the reference's 128), the batch's pixels drawn from it without
+replacement on the device, each ray's colour error folded back into it.
 
-Not here: --error_map importance sampling, patch sampling,
---color_space linear, more than one image per batch."""
+Not here: patch sampling, --color_space linear, more than one
+image per batch."""
 import argparse
 import math
 import os
@@ -41,6 +45,9 @@ def get_parser():
     p.add_argument("--depth_loss_weight", type=float, default=0.0,
                    help="weight of the masked L1 depth loss (needs a dep_path per frame)")
     p.add_argument("--color_loss_weight", type=float, default=1.0, help="weight of the colour MSE")
+    p.add_argument("--error_map", action="store_true", help="use error map to sample rays")
+    p.add_argument("--error_map_res", type=int, default=128,
+                   help="cells a side of each view's error map (1..128; needs num_rays <= its square)")
     # dataset options
     p.add_argument("--downscale", type=int, default=1)
     p.add_argument("--bound", type=float, default=2,
@@ -83,7 +90,11 @@ def main(argv=None):
     bound = int(opt.bound) if float(opt.bound).is_integer() else opt.bound
     data_args = dict(downscale=opt.downscale, scale=opt.scale, offset=opt.offset, store="uint8",
                      depth_scale=opt.depth_scale)
-    train = NeRFDataset(opt.path, dev, type="train", num_rays=opt.num_rays, **data_args)
+    try:
+        train = NeRFDataset(opt.path, dev, type="train", num_rays=opt.num_rays, error_map=opt.error_map,
+                            error_map_res=opt.error_map_res, **data_args)
+    except ValueError as e:  # e.g. an error map resolution out of range
+        sys.exit(f"[main_nerf] {e}")
     model = NeRFNetwork(encoding="hashgrid", bound=bound, cuda_ray=True, density_scale=1, min_near=opt.min_near,
                         density_thresh=opt.density_thresh).to(dev)
     model.train()
@@ -96,7 +107,8 @@ def main(argv=None):
     except ValueError as e:  # e.g. a depth weight on a scene without depth maps
         sys.exit(f"[main_nerf] {e}")
     print(f"[main_nerf] {train.images.shape[0]} images {train.H}x{train.W}x{train.images.shape[3]} "
-          f"({train.images.numel() / 2 ** 20:.0f} MiB uint8), {opt.num_rays} rays/step, sample budget {M}")
+          f"({train.images.numel() / 2 ** 20:.0f} MiB uint8), {opt.num_rays} rays/step, sample budget {M}"
+          + (f", error map {opt.error_map_res}x{opt.error_map_res}" if opt.error_map else ""))
 
     every = max(1, int(opt.update_extra_interval))
     log_every = max(every, opt.iters // 20 // every * every)

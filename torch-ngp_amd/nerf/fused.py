@@ -16,6 +16,9 @@ With loss weights other than the defaults (depth_loss_weight > 0 or
 color_loss_weight != 1) the draws also gather each ray's depth from the
 dataset's depth maps and the composite runs its depth form
 (ngp_nerf_composite_loss_depth); the launches are the same.
+On a dataset with an error map (the reference's --error_map, DESIGN.md section
+13) two launches join them: ngp_error_map_select just before the launch that
+draws, ngp_error_map_update just after the composite.
 
 Static shapes: N rays per step, M = the sample buffer (mean_count); rows past
 the marcher's sample count are skipped on the device, so a fixed M costs
@@ -36,6 +39,7 @@ scan/emit are both memory-bound and slowed each other more than they
 overlapped (profiles/r01u_overlap_trace.txt).
 """
 import ctypes
+import math
 import os
 import sys
 
@@ -96,11 +100,22 @@ DEFAULT_OPTIONS = dict(table16=False, split_head=False, split_reduce=False, spli
                        density_run_max=False)
 
 
+def perm_mult(n):
+    """The multiplier of the error-map draw's ray permutation, ray i -> selected
+    rank (i * perm_mult + r) % n: the largest integer <= 0.618 n coprime to n
+    (at least 1), so consecutive ray indices land far apart in the ascending
+    cell list."""
+    p = int(0.618 * n)
+    while p > 1 and math.gcd(p, n) != 1:
+        p -= 1
+    return max(p, 1)
+
+
 class FusedTrainer:
     def __init__(self, model, dataset, M, lr=1e-2, iters=30000, max_steps=1024, T_thresh=1e-4,
                  dt_gamma=0.0, seed=0, betas=(0.9, 0.99), eps=1e-15, init_scale=65536.0,
                  growth_interval=2000, distributed=False, grid_timing=False, options=None,
-                 depth_loss_weight=0.0, color_loss_weight=1.0):
+                 depth_loss_weight=0.0, color_loss_weight=1.0, error_map=None):
         """distributed: ray-sharded data parallelism over the initialised
         torch.distributed group: each rank draws its own rays; the flat fp16
         gradient is averaged with one RCCL reduce-scatter, each rank's Adam
@@ -117,7 +132,16 @@ class FusedTrainer:
         the colour-only one, launch for launch; otherwise the draws gather each
         ray's depth beside its colour and the composite runs its depth form
         (ngp_nerf_composite_loss_depth). Data parallel: the same launches on
-        every rank (the loss is a per-rank mean, the gradients are averaged)."""
+        every rank (the loss is a per-rank mean, the gradients are averaged).
+        error_map: the reference's --error_map importance sampling (DESIGN.md
+        section 13) on `dataset.error_map`, a float32 [n_poses, res * res] map
+        of ones (nerf.provider.NeRFDataset(error_map=True)): each draw takes its
+        pixels from N map cells of the drawn image chosen without replacement
+        with the map as weights (ngp_error_map_select, one launch before the
+        launch that draws), and each step folds its rays' colour errors back
+        into those cells (ngp_error_map_update, one launch after the
+        composite). None: on exactly when the dataset has a map; False: the
+        uniform draw, launch for launch, whatever the dataset has. World 1 only."""
         opts = dict(DEFAULT_OPTIONS)
         for k, v in (options or {}).items():
             if k not in opts:
@@ -314,6 +338,49 @@ class FusedTrainer:
             lj.depth_min, lj.depth_max = float(model.min_near), float(model.bound)
             lj.out_depth, lj.loss_depth_ray = nat.ptr(self.out_depth), nat.ptr(self.loss_depth_ray)
             self._loss_job = lj
+        # error-map sampling: the draws take their pixels from `selected`, the N
+        # cells ngp_error_map_select drew from the image's map, and write each
+        # ray's cell to `coarse`; the composite's image then feeds the map's EMA
+        emap = getattr(dataset, "error_map", None)
+        if error_map is None:
+            error_map = emap is not None
+        self._emap = None
+        if error_map:
+            if emap is None:
+                raise ValueError("FusedTrainer: error_map=True needs a dataset with an error map "
+                                 "(nerf.provider.NeRFDataset(..., error_map=True)); this one has none")
+            if self._src is None:
+                raise ValueError("FusedTrainer: error-map sampling needs an image dataset (dataset.images); "
+                                 "the analytic boxes have no per-image map")
+            if self.world > 1:
+                raise ValueError(f"FusedTrainer: error-map sampling is single-process only (world size "
+                                 f"{self.world}): every rank would keep its own map")
+            n_poses = int(dataset.poses.shape[0])
+            res = int(getattr(dataset, "error_map_res", 0) or 0)
+            if not 1 <= res <= 128:
+                raise ValueError(f"FusedTrainer: dataset.error_map_res must be in 1..128, got {res}")
+            if (not torch.is_tensor(emap) or tuple(emap.shape) != (n_poses, res * res)
+                    or emap.dtype != torch.float32 or not emap.is_contiguous()):
+                raise ValueError(f"FusedTrainer: dataset.error_map must be contiguous float32 [n_poses, res * res] = "
+                                 f"[{n_poses}, {res * res}], got {getattr(emap, 'dtype', type(emap))} "
+                                 f"{list(getattr(emap, 'shape', []))}"
+                                 f"{'' if not torch.is_tensor(emap) or emap.is_contiguous() else ' (not contiguous)'}")
+            if emap.device != dev:
+                raise ValueError(f"FusedTrainer: dataset.error_map is on {emap.device}, the model on {dev}")
+            if N > res * res:
+                raise ValueError(f"FusedTrainer: num_rays {N} > the error map's {res} x {res} = {res * res} cells "
+                                 "(they are drawn without replacement)")
+            if not opts["split_head"] and not opts["march_adam"] and not self._dist:
+                raise ValueError("FusedTrainer: option march_adam=False draws the batch in the Adam head launch, "
+                                 "which has no image draw and no error-map draw; keep march_adam, or set "
+                                 "split_head=True as well")
+            self._emap, self._emap_res = emap, res
+            self.coarse, self.selected = z(N, dtype=torch.int32), z(N, dtype=torch.int32)
+            self.out_image = z(N, 3)
+            src = self._src
+            src.error_map, src.error_map_res = nat.ptr(emap), res
+            src.selected, src.coarse = nat.ptr(self.selected), nat.ptr(self.coarse)
+            src.perm_mult = perm_mult(N)
         # World 1: the grid forward reads the fp32 table and rounds each value to
         # half as it loads it (the same values autocast's cast gives), so Adam
         # does not write an fp16 copy of the table (2 of its 28 B / parameter).
@@ -885,6 +952,7 @@ class FusedTrainer:
         # the batch source: the analytic boxes, or the dataset's image stack
         head, source = ((lib.ngp_fused_step_head, (self._boxes, self._nboxes)) if self._src is None else
                         (lib.ngp_fused_step_head_images, (ctypes.byref(self._src),)))
+        self._select()
         nat.check(head(P(d.poses), d.poses.shape[0], self._intr, d.H, d.W, self.N,
                        *source, self._aabb, float(m.min_near), self.seed,
                        P(self.state), P(self.rays_o), P(self.rays_d), P(self.rgba), P(self.bg),
@@ -895,6 +963,18 @@ class FusedTrainer:
                        self._grid_counter_bytes, s),
                   "fused_step_head")
         self._tick("step_head")
+
+    def _select(self):
+        """Error-map sampling: the cells of the draw the next launch makes
+        (ngp_error_map_select reads the draw counter and the drawn image's map
+        row on the device), issued just before that launch."""
+        if self._emap is None:
+            return
+        d = self.data
+        nat.check(nat.lib().ngp_error_map_select(nat.ptr(self._emap), d.poses.shape[0], self._emap_res, self.N,
+                                                 self.seed, nat.ptr(self.state), nat.ptr(self.selected), None,
+                                                 nat.stream_of(self.rays_o)), "error_map_select")
+        self._tick("error_map_select")
 
     def _forward_backward(self):
         """march -> network -> composite + MSE -> full backward into the fp16 grads
@@ -976,27 +1056,36 @@ class FusedTrainer:
         live = self._live and draw
         if live:
             lv = self._live_bufs
+        # error-map sampling: the composite also writes its image, which the map's update reads
+        img_out = P(self.out_image) if self._emap is not None else None
         if self._loss_job is not None:
             # the depth-supervised loss (and its weights): one entry for both row forms
             job = self._loss_job_live if live else self._loss_job
             chk(lib.ngp_nerf_composite_loss_depth(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                                   P(self.rays), M, N, self.T_thresh, float(m.density_scale),
                                                   P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
-                                                  P(self.g_h), None, None, P(self.loss_ray), ctypes.byref(job), s),
+                                                  P(self.g_h), img_out, None, P(self.loss_ray), ctypes.byref(job), s),
                 "composite_loss_depth")
         elif live:
             chk(lib.ngp_nerf_composite_loss_live(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                                  P(self.rays), M, N, self.T_thresh, float(m.density_scale),
                                                  P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
-                                                 P(self.g_h), None, None, P(self.loss_ray), P(lv["ray_rows"]),
+                                                 P(self.g_h), img_out, None, P(self.loss_ray), P(lv["ray_rows"]),
                                                  P(lv["cnt"]), P(lv["rows"]), P(lv["total"]), s),
                 "composite_loss_live")
         else:
             chk(lib.ngp_nerf_composite_loss(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                             P(self.rays), M, N, self.T_thresh, float(m.density_scale),
                                             P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
-                                            P(self.g_h), None, None, P(self.loss_ray), s), "composite_loss")
+                                            P(self.g_h), img_out, None, P(self.loss_ray), s), "composite_loss")
         self._tick("composite_loss")
+        if self._emap is not None:
+            # each ray's colour error into its cell of the drawn image's map (before the
+            # next draw's select, which the stream orders after this launch)
+            chk(lib.ngp_error_map_update(P(self._emap), self.data.poses.shape[0], self._emap_res, N, P(self.rays),
+                                         img_out, P(self.rgba), 4, P(self.bg), P(self.image_index), P(self.coarse),
+                                         s), "error_map_update")
+            self._tick("error_map_update")
         if self._one_bwd:  # both networks' backward in one launch (ngp_nerf_backward)
             timing = P(self.grid_ws) + self._grid_timing_at if self._grid_timing_at else None
             if live:
@@ -1048,6 +1137,7 @@ class FusedTrainer:
             # + the next step's batch from the image stack (one entry for both
             # row forms: the live rows, or every row below the sample count)
             rows, n = (P(self._live_bufs["rows"]), P(self._live_bufs["total"])) if self._live else (None, cnt)
+            self._select()
             iargs = (P(self.g_enc), P(self.xyzs), float(m.bound), P(e.offsets), P(self.grads[0]), M, rows, n,
                      *grid_args[:-1], self._offsets_host, P(self.grid_ws), self.grid_ws.numel(), self._grid_flags,
                      self._inf_flag)
@@ -1554,6 +1644,8 @@ class FusedTrainer:
                  # draw: batches drawn; ahead: the last of them is the next step's (drawn during
                  # the last backward, draw_ahead), which a restored trainer draws again
                  "fused": {"draw": int(si[self._S_DRAW]), "ahead": int(self._ahead)}}
+        if self._emap is not None:
+            state["error_map"] = self._emap.detach().cpu().clone()
         if full:
             m1, m2 = self._moments()
             # param indices follow model.get_params: encoder [0], sigma_net [1], encoder_dir [], color_net [2]
@@ -1598,6 +1690,8 @@ class FusedTrainer:
         si = self.state.view(torch.int32)
         si[self._S_ITER] = int(state.get("global_step", 0))
         self._ahead = False
+        if self._emap is not None and state.get("error_map") is not None:
+            self._emap.copy_(state["error_map"].to(self.dev, torch.float32).reshape(self._emap.shape))
         if "fused" in state:
             draw = int(state["fused"]["draw"])
             if state["fused"].get("ahead"):

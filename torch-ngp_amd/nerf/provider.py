@@ -201,10 +201,17 @@ class NeRFDataset:
     floor(i * src / dst)). Every frame has one or none has (`depths` None).
     depth_scale: file units -> ngp units, gt = depth * depth_scale (default: the
     pose `scale`; the reference's 2 * bound / aabb_size is the caller's to
-    pass); sample() returns "depths" [1, N] in ngp units (:555-557)."""
+    pass); sample() returns "depths" [1, N] in ngp units (:555-557).
+    error_map (the reference's --error_map, :397-401): for type "train",
+    `error_map` is a float32 [n, error_map_res ** 2] tensor of ones on the
+    device, a coarse error image per view, cell = row_cell * res + col_cell;
+    otherwise None. sample() then draws its pixels from the map (get_rays'
+    error_map branch) and returns their cells as "inds_coarse"; the trainers
+    fold each ray's loss back into the map. error_map_res: 1..128 (the
+    reference's fixed 128)."""
 
     def __init__(self, path, device, type="train", downscale=1, scale=0.33, offset=(0, 0, 0), num_rays=4096,
-                 store="float32", depth_scale=None):
+                 store="float32", depth_scale=None, error_map=False, error_map_res=128):
         import json
         import os
 
@@ -213,6 +220,9 @@ class NeRFDataset:
         if store not in ("float32", "uint8"):
             raise ValueError(f"NeRFDataset: store must be 'float32' or 'uint8', got {store!r}")
         self.device, self.num_rays, self.store = device, num_rays, store
+        self.error_map_res = int(error_map_res)
+        if error_map_res != self.error_map_res or not 1 <= self.error_map_res <= 128:
+            raise ValueError(f"NeRFDataset: error_map_res must be an integer in 1..128, got {error_map_res!r}")
         if os.path.exists(os.path.join(path, "transforms.json")):
             self.mode = "colmap"
             with open(os.path.join(path, "transforms.json")) as f:
@@ -269,6 +279,8 @@ class NeRFDataset:
         self.H, self.W = H, W
         self.depths = torch.from_numpy(np.ascontiguousarray(np.stack(depths))).to(device) if depths else None
         self.depth_scale = float(scale if depth_scale is None else depth_scale)
+        self.error_map = (torch.ones(len(poses), self.error_map_res ** 2, dtype=torch.float32, device=device)
+                          if error_map and type == "train" else None)
         self.poses = torch.from_numpy(np.stack(poses)).to(device)
         self.images = torch.from_numpy(np.stack(images)).to(device)
         # the uint8 store's divisor as a tensor: a true division on every device
@@ -293,7 +305,9 @@ class NeRFDataset:
         if index is None:
             index = int(torch.randint(0, self.poses.shape[0], (1,), generator=generator).item())
         poses = self.poses[index:index + 1]
-        rays = get_rays(poses, self.intrinsics, self.H, self.W, self.num_rays, generator=generator)
+        error_map = None if self.error_map is None else self.error_map[index:index + 1]
+        rays = get_rays(poses, self.intrinsics, self.H, self.W, self.num_rays, error_map=error_map,
+                        generator=generator)
         C = self.images.shape[-1]
         images = torch.gather(self.images[index:index + 1].view(1, -1, C), 1,
                               rays["inds"].unsqueeze(-1).expand(1, rays["inds"].shape[-1], C))
@@ -301,6 +315,8 @@ class NeRFDataset:
             images = images.float() / self._div
         out = {"H": self.H, "W": self.W, "rays_o": rays["rays_o"], "rays_d": rays["rays_d"], "images": images,
                "index": index}
+        if "inds_coarse" in rays:
+            out["inds_coarse"] = rays["inds_coarse"]  # the cells to fold the loss back into (utils.py:113)
         if self.depths is not None:
             # the same pixels' depths, in ngp units (one fp32 multiply, as the fused engine's gather)
             out["depths"] = torch.gather(self.depths[index:index + 1].view(1, -1), 1, rays["inds"]) * self.depth_scale

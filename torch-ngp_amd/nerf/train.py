@@ -43,7 +43,9 @@ class Trainer:
         """depth_loss_weight, color_loss_weight: the reference's pixel loss
         color_loss_weight * rgb + depth_loss_weight * dep (nerf/utils.py:951-954)
         on batches that carry "depths" (:545-553). perturb: the march's jitter
-        (off for comparisons on a fixed batch)."""
+        (off for comparisons on a fixed batch). A dataset with an `error_map`
+        (NeRFDataset(error_map=True)) draws its batches from it, and each
+        ray's colour MSE is folded back into its cell (utils.py:578-600)."""
         self.model = model
         self.dataset = dataset
         self.fp16 = fp16
@@ -81,7 +83,13 @@ class Trainer:
                                         bg_color=bg_color, perturb=self.perturb, force_all_rays=False,
                                         dt_gamma=self.dt_gamma, max_steps=self.max_steps)
             pred_rgb = outputs["image"]
-            loss = ((pred_rgb - gt_rgb) ** 2).mean(-1).mean()
+            loss_ray = ((pred_rgb - gt_rgb) ** 2).mean(-1)  # [B, N]
+            loss = loss_ray.mean()
+            if "inds_coarse" in data and getattr(self.dataset, "error_map", None) is not None:
+                # the reference's EMA of each ray's colour error into its map cell (utils.py:578-600)
+                row = self.dataset.error_map[data["index"]]
+                inds = data["inds_coarse"][0]
+                row[inds] = 0.1 * row[inds] + 0.9 * loss_ray.detach()[0].float().to(row.device)
             if "depths" in data:
                 # the reference's masked L1 on the composite's depth (utils.py:545-553), both in ngp units
                 gt_dep, pred_dep = data["depths"], outputs["depth_bound_scale"]
