@@ -957,6 +957,39 @@ int ngp_mesh_emit(const float* volume, uint32_t nx, uint32_t ny, uint32_t nz, fl
                   const void* ws, size_t ws_bytes, uint64_t V, uint64_t T, float* vertices, float* normals,
                   int32_t* faces, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Whole frames around the device-driven render loop (replaces the per-frame */
+/* get_rays + near_far + render_init before it and the blend / quantisation  */
+/* of Trainer.test after it, nerf/utils.py:656-685, 743-796)                 */
+/* ------------------------------------------------------------------------ */
+
+/* One launch before the loop: all N = H * W rays of pose `pose_index` of the
+ * device stack poses f32 [n_poses, 4, 4], pixel p = row * W + col (get_rays
+ * with N = -1, utils.py:52-136, in the arithmetic of the training draw,
+ * ngp_image_rays, bit for bit), nears / fars as ngp_near_far_from_aabb gives
+ * them, noises = 0, and what ngp_render_init sets: alive list 0 = arange(N),
+ * rays_t = nears, weights_sum / depth / image = 0, the loop state.
+ * intrinsics4 (fx, fy, cx, cy) and aabb6 are on the host. Buffers are [N] or
+ * [N, 3], 16-byte aligned. Null buffers, H * W outside [1, 2^28), pose_index
+ * >= n_poses or a misaligned buffer: NGP_ERR_ARG before any device work. */
+int ngp_frame_begin(const float* poses, uint32_t n_poses, uint32_t pose_index, const float* intrinsics4, uint32_t H,
+                    uint32_t W, const float* aabb6, float min_near, float* rays_o, float* rays_d, float* nears,
+                    float* fars, float* noises, int32_t* rays_alive, float* rays_t, float* weights_sum, float* depth,
+                    float* image, void* state, void* stream);
+/* One launch after the loop has ended, per pixel p:
+ *   c = image[p] + (1 - weights_sum[p]) * bg_color       (each of 3 channels)
+ *   z = max(depth[p] - nears[p], 0) / (fars[p] - nears[p])  (a NaN stays one;
+ *       a ray that misses the box has near == far: 0 / 0)
+ * in fp32 without contraction, then rgb8 u8 [H, W, 3] = q(c), depth8 u8 [H, W]
+ * = q(z) with q(x) = (uint8)(clamp(x, 0, 1) * 255.0f), truncating, 0 for a
+ * non-finite x: the reference's (x * 255).astype(np.uint8), made total.
+ * image_out f32 [N, 3] / depth_out f32 [N] (each nullable) receive c and z.
+ * Float buffers 16-byte aligned, uint8 outputs 4-byte aligned. Null required
+ * buffers, H * W outside [1, 2^28), misalignment: NGP_ERR_ARG. */
+int ngp_frame_finish(uint32_t H, uint32_t W, const float* image, const float* weights_sum, const float* depth,
+                     const float* nears, const float* fars, float bg_color, uint8_t* rgb8, uint8_t* depth8,
+                     float* image_out, float* depth_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,9 @@ SIGNATURES = {
     "ngp_mesh_count": [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_sz, c_vp, c_vp],
     "ngp_mesh_emit": [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_vp, c_sz, ctypes.c_uint64, ctypes.c_uint64,
                       c_vp, c_vp, c_vp, c_vp],
+    "ngp_frame_begin": [c_vp, c_u32, c_u32, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_frame_finish": [c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {
     "ngp_last_error": ctypes.c_char_p,

@@ -1,0 +1,218 @@
+// Whole frames around the device-driven render loop (raymarching.hip,
+// nerf/fused_render.py): the reference's test render (Trainer.test /
+// test_step, nerf/utils.py:656-685, 743-796) renders every ray of a pose,
+// quantises colour and depth to uint8 and writes PNGs. DESIGN.md §14.
+//
+//   k_frame_begin   one launch before the loop: the rays of all H * W pixels of
+//                   one pose of a device pose stack (get_rays with N = -1,
+//                   utils.py:52-136, through ngp_head::pixel_ray, the training
+//                   draw's arithmetic), their near / far (ngp_head::near_far),
+//                   zeroed noises, and everything ngp_render_init initialises
+//   k_frame_finish  one launch after it: background blend, depth
+//                   normalisation and the uint8 quantisation
+//
+// Both make one pass over the pixels and are bound by memory. A thread owns 4
+// consecutive pixels, so every [N] array moves as one 16-byte access per
+// thread, every [N, 3] array as three, the 12 colour bytes as three dwords and
+// the 4 depth bytes as one. The last N % 4 pixels of a frame go element by
+// element (one thread).
+#include "ngp_common.h"
+#include "ngp_head.h"
+#include "ngp_render.h"
+
+#include <cmath>
+
+namespace {
+
+using ngp_render::RenderSlot;
+
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kPix = 4;  // pixels per thread
+
+// K floats of a thread's run starting at dst / src (16-byte aligned when
+// `full`): K / 4 vector accesses, or the first `live` elements one by one.
+template <int K> NGP_DEV void put(float* dst, const float (&v)[K], bool full, uint32_t live) {
+    if (full) {
+#pragma unroll
+        for (int q = 0; q < K / 4; ++q)
+            reinterpret_cast<float4*>(dst)[q] = make_float4(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            if ((uint32_t)k < live) dst[k] = v[k];
+    }
+}
+template <int K> NGP_DEV void get(const float* __restrict__ src, float (&v)[K], bool full, uint32_t live) {
+    if (full) {
+#pragma unroll
+        for (int q = 0; q < K / 4; ++q) {
+            const float4 t = reinterpret_cast<const float4*>(src)[q];
+            v[q * 4] = t.x; v[q * 4 + 1] = t.y; v[q * 4 + 2] = t.z; v[q * 4 + 3] = t.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] = (uint32_t)k < live ? src[k] : 0.0f;
+    }
+}
+
+struct FrameCamera {
+    float fx, fy, cx, cy;
+    uint32_t W, N;  // N = H * W
+    float aabb[6];
+    float min_near;
+};
+
+struct FrameRays {
+    float *rays_o, *rays_d, *nears, *fars, *noises, *rays_t, *weights_sum, *depth, *image;
+    int32_t* rays_alive;
+    RenderSlot* state;
+};
+
+__global__ void __launch_bounds__(kThreads)
+k_frame_begin(const float* __restrict__ pose, FrameCamera cam, FrameRays out) {
+    const uint32_t g = blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t p0 = g * kPix;
+    if (g == 0) {  // ngp_render_init's loop state
+        out.state[0] = RenderSlot{0, (int32_t)cam.N, 0, 0};
+        out.state[1] = RenderSlot{0, 0, 0, 0};
+    }
+    if (p0 >= cam.N) return;
+    const uint32_t cnt = min(kPix, cam.N - p0);
+    const bool full = cnt == kPix;
+    float ro[kPix * 3], rd[kPix * 3], nr[kPix], fr[kPix], alive[kPix];
+    const float zero1[kPix] = {}, zero3[kPix * 3] = {};
+#pragma unroll
+    for (uint32_t k = 0; k < kPix; ++k) {
+        // (pixels past the frame, in the tail's thread only, are computed and not stored)
+        const uint32_t pix = min(p0 + k, cam.N - 1u);
+        float o[3], d[3];
+        ngp_head::pixel_ray(pix, cam.W, cam.fx, cam.fy, cam.cx, cam.cy, pose, o, d);
+        ngp_head::near_far(o, d, cam.aabb, cam.min_near, nr[k], fr[k]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            ro[k * 3 + c] = o[c];
+            rd[k * 3 + c] = d[c];
+        }
+        alive[k] = __int_as_float((int32_t)(p0 + k));
+    }
+    put(out.rays_o + (size_t)p0 * 3, ro, full, cnt * 3);
+    put(out.rays_d + (size_t)p0 * 3, rd, full, cnt * 3);
+    put(out.nears + p0, nr, full, cnt);
+    put(out.fars + p0, fr, full, cnt);
+    put(out.rays_t + p0, nr, full, cnt);  // the march starts at near
+    put(reinterpret_cast<float*>(out.rays_alive) + p0, alive, full, cnt);  // alive list 0 = arange(N)
+    put(out.noises + p0, zero1, full, cnt);  // perturb = False
+    put(out.weights_sum + p0, zero1, full, cnt);
+    put(out.depth + p0, zero1, full, cnt);
+    put(out.image + (size_t)p0 * 3, zero3, full, cnt * 3);
+}
+
+// The reference's (x * 255).astype(np.uint8) (utils.py:776, :779) made total:
+// x clamped to [0, 1], truncated; a non-finite x gives 0.
+NGP_DEV uint32_t quantise(float x) {
+    if (!(fabsf(x) < INFINITY)) return 0u;
+    return (uint32_t)(fminf(fmaxf(x, 0.0f), 1.0f) * 255.0f);
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_frame_finish(uint32_t N, const float* __restrict__ image, const float* __restrict__ weights_sum,
+               const float* __restrict__ depth, const float* __restrict__ nears, const float* __restrict__ fars,
+               float bg, uint8_t* __restrict__ rgb8, uint8_t* __restrict__ depth8, float* __restrict__ image_out,
+               float* __restrict__ depth_out) {
+    const uint32_t p0 = (blockIdx.x * kThreads + threadIdx.x) * kPix;
+    if (p0 >= N) return;
+    const uint32_t cnt = min(kPix, N - p0);
+    const bool full = cnt == kPix;
+    float im[kPix * 3], ws[kPix], dp[kPix], nr[kPix], fr[kPix];
+    get(image + (size_t)p0 * 3, im, full, cnt * 3);
+    get(weights_sum + p0, ws, full, cnt);
+    get(depth + p0, dp, full, cnt);
+    get(nears + p0, nr, full, cnt);
+    get(fars + p0, fr, full, cnt);
+    float c[kPix * 3], z[kPix];
+    uint32_t cq[kPix * 3], zq[kPix];
+#pragma unroll
+    for (uint32_t k = 0; k < kPix; ++k) {
+        // FusedRenderer.render: image + (1 - weights_sum) * bg_color,
+        // clamp(depth - nears, min=0) / (fars - nears), operation for operation
+        const float w = (1.0f - ws[k]) * bg;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            c[k * 3 + j] = im[k * 3 + j] + w;
+            cq[k * 3 + j] = quantise(c[k * 3 + j]);
+        }
+        const float t = dp[k] - nr[k];
+        z[k] = (t < 0.0f ? 0.0f : t) / (fr[k] - nr[k]);  // torch.clamp keeps a NaN; near == far (a miss): 0 / 0
+        zq[k] = quantise(z[k]);
+    }
+    if (full) {
+        uint32_t* rgb = reinterpret_cast<uint32_t*>(rgb8 + (size_t)p0 * 3);
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            rgb[q] = cq[q * 4] | (cq[q * 4 + 1] << 8) | (cq[q * 4 + 2] << 16) | (cq[q * 4 + 3] << 24);
+        *reinterpret_cast<uint32_t*>(depth8 + p0) = zq[0] | (zq[1] << 8) | (zq[2] << 16) | (zq[3] << 24);
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < kPix; ++k) {
+            if (k >= cnt) break;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) rgb8[(size_t)(p0 + k) * 3 + j] = (uint8_t)cq[k * 3 + j];
+            depth8[p0 + k] = (uint8_t)zq[k];
+        }
+    }
+    if (image_out) put(image_out + (size_t)p0 * 3, c, full, cnt * 3);
+    if (depth_out) put(depth_out + p0, z, full, cnt);
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+int check_frame_size(uint32_t H, uint32_t W, const char* who) {
+    NGP_REQUIRE(H >= 1 && W >= 1 && (uint64_t)H * W <= 0x7fffffffu / 8u, NGP_ERR_ARG,
+                "%s: H * W must be in [1, 2^28), got %u x %u", who, H, W);
+    return NGP_OK;
+}
+
+}  // namespace
+
+extern "C" int ngp_frame_begin(const float* poses, uint32_t n_poses, uint32_t pose_index, const float* intrinsics4,
+                               uint32_t H, uint32_t W, const float* aabb6, float min_near, float* rays_o,
+                               float* rays_d, float* nears, float* fars, float* noises, int32_t* rays_alive,
+                               float* rays_t, float* weights_sum, float* depth, float* image, void* state,
+                               void* stream) {
+    if (int e = check_frame_size(H, W, "frame_begin")) return e;
+    NGP_REQUIRE(poses && intrinsics4 && aabb6 && state && rays_o && rays_d && nears && fars && noises &&
+                    rays_alive && rays_t && weights_sum && depth && image,
+                NGP_ERR_ARG, "frame_begin: null buffer");
+    NGP_REQUIRE(pose_index < n_poses, NGP_ERR_ARG, "frame_begin: pose %u of a stack of %u", pose_index, n_poses);
+    NGP_REQUIRE(aligned16(rays_o) && aligned16(rays_d) && aligned16(nears) && aligned16(fars) && aligned16(noises) &&
+                    aligned16(rays_alive) && aligned16(rays_t) && aligned16(weights_sum) && aligned16(depth) &&
+                    aligned16(image) && aligned16(state),
+                NGP_ERR_ARG, "frame_begin: the ray buffers must be 16-byte aligned");
+    FrameCamera cam;
+    cam.fx = intrinsics4[0]; cam.fy = intrinsics4[1]; cam.cx = intrinsics4[2]; cam.cy = intrinsics4[3];
+    cam.W = W;
+    cam.N = H * W;
+    for (int k = 0; k < 6; ++k) cam.aabb[k] = aabb6[k];
+    cam.min_near = min_near;
+    const FrameRays out{rays_o, rays_d, nears, fars, noises, rays_t, weights_sum, depth, image, rays_alive,
+                        static_cast<RenderSlot*>(state)};
+    k_frame_begin<<<ngp_div_up(ngp_div_up(cam.N, kPix), kThreads), kThreads, 0, ngp_stream(stream)>>>(
+        poses + (size_t)pose_index * 16, cam, out);
+    return ngp_check_launch("frame_begin");
+}
+
+extern "C" int ngp_frame_finish(uint32_t H, uint32_t W, const float* image, const float* weights_sum,
+                                const float* depth, const float* nears, const float* fars, float bg_color,
+                                uint8_t* rgb8, uint8_t* depth8, float* image_out, float* depth_out, void* stream) {
+    if (int e = check_frame_size(H, W, "frame_finish")) return e;
+    NGP_REQUIRE(image && weights_sum && depth && nears && fars && rgb8 && depth8, NGP_ERR_ARG,
+                "frame_finish: null buffer");
+    NGP_REQUIRE(aligned16(image) && aligned16(weights_sum) && aligned16(depth) && aligned16(nears) &&
+                    aligned16(fars) && aligned16(image_out) && aligned16(depth_out) &&
+                    (reinterpret_cast<uintptr_t>(rgb8) & 3u) == 0 && (reinterpret_cast<uintptr_t>(depth8) & 3u) == 0,
+                NGP_ERR_ARG, "frame_finish: float buffers must be 16-byte aligned, uint8 outputs 4-byte aligned");
+    const uint32_t N = H * W;
+    k_frame_finish<<<ngp_div_up(ngp_div_up(N, kPix), kThreads), kThreads, 0, ngp_stream(stream)>>>(
+        N, image, weights_sum, depth, nears, fars, bg_color, rgb8, depth8, image_out, depth_out);
+    return ngp_check_launch("frame_finish");
+}

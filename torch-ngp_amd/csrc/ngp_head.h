@@ -76,6 +76,24 @@ NGP_DEV void near_far(const float o[3], const float d[3], const float aabb[6], f
     if (near < min_near) near = min_near;
 }
 
+// The ray of flat pixel `pix` = row * W + col of the camera P (row-major 4 x 4,
+// camera to world): get_rays (utils.py:52-136): pixel centre, camera
+// direction, normalise, rotate. The one statement of it for the training draw
+// (lego_ray) and the frame renderer (frame.hip).
+NGP_DEV void pixel_ray(uint32_t pix, uint32_t W, float fx, float fy, float cx, float cy,
+                       const float* __restrict__ P, float (&o)[3], float (&d)[3]) {
+    const float i = (float)(pix % W) + 0.5f;
+    const float j = (float)(pix / W) + 0.5f;
+    float xs = (i - cx) / fx, ys = (j - cy) / fy, zs = 1.0f;
+    const float nrm = sqrtf(xs * xs + ys * ys + zs * zs);
+    xs /= nrm; ys /= nrm; zs /= nrm;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        d[k] = fmaf(zs, P[k * 4 + 2], fmaf(ys, P[k * 4 + 1], xs * P[k * 4 + 0]));
+        o[k] = P[k * 4 + 3];
+    }
+}
+
 struct LegoOut {
     float *rays_o, *rays_d, *rgba, *bg, *nears, *fars, *noises;
     int32_t *counter, *step_counter;
@@ -231,16 +249,9 @@ NGP_DEV void lego_ray(uint32_t n, uint32_t N, uint32_t it, const float* __restri
     } else {
         pix = rng_u32(sc.seed, it, n, 1) % (sc.H * sc.W);
     }
-    // get_rays (utils.py:52-136): pixel centre, camera direction, normalise, rotate
-    const float i = (float)(pix % sc.W) + 0.5f;
-    const float j = (float)(pix / sc.W) + 0.5f;
-    float xs = (i - sc.cx) / sc.fx, ys = (j - sc.cy) / sc.fy, zs = 1.0f;
-    const float nrm = sqrtf(xs * xs + ys * ys + zs * zs);
-    xs /= nrm; ys /= nrm; zs /= nrm;
+    pixel_ray(pix, sc.W, sc.fx, sc.fy, sc.cx, sc.cy, P, o, d);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        d[k] = fmaf(zs, P[k * 4 + 2], fmaf(ys, P[k * 4 + 1], xs * P[k * 4 + 0]));
-        o[k] = P[k * 4 + 3];
         out.rays_o[n * 3 + k] = o[k];
         out.rays_d[n * 3 + k] = d[k];
     }

@@ -25,6 +25,7 @@
 #include "ngp_common.h"
 #include "ngp_dpp.h"
 #include "ngp_head.h"
+#include "ngp_render.h"
 #include "ngp_step.h"
 
 #include <algorithm>
@@ -1227,12 +1228,7 @@ k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* ray
 // once per replay. Per ray everything is the reference's arithmetic: the
 // list's order only moves a ray's samples to other rows, and the grid / MLP
 // kernels compute every row from that row alone.
-struct RenderSlot {
-    int32_t count;    // samples this iteration: n_alive * n_step (0 once done); the grid / MLP count
-    int32_t n_alive;  // rays in this iteration's alive list
-    int32_t step;     // the reference's `step` before this iteration
-    int32_t pad;
-};
+using ngp_render::RenderSlot;  // ngp_render.h
 
 NGP_DEV bool render_live(const RenderSlot& s, uint32_t max_steps) {
     return s.n_alive > 0 && (uint32_t)s.step < max_steps;

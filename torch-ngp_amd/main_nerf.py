@@ -16,9 +16,15 @@ loss is color_loss_weight * rgb + depth_loss_weight * dep (nerf/utils.py
 578-600): a coarse error image per training view (--error_map_res cells a
 side, the reference's 128), the batch's pixels drawn from it without
 replacement on the device, each ray's colour error folded back into it.
+--test trains nothing: it loads <workspace>/checkpoints/ngp.pth (--ckpt),
+renders the test split's poses, or --test_frames steps between two training
+poses where the scene has no transforms_test.json, and writes
+<workspace>/results/ngp_<i>_rgb.png and _depth.png, as the reference's
+trainer.test does (main_nerf.py:188 / :239); --write_frames does the same at
+the end of a training run. The frames are made on the device (nerf/frames.py).
 
 Not here: patch sampling, --color_space linear, more than one
-image per batch."""
+image per batch, video files, resuming training from a checkpoint."""
 import argparse
 import math
 import os
@@ -64,6 +70,14 @@ def get_parser():
     p.add_argument("--save_mesh", action="store_true", help="write <workspace>/meshes/ngp.ply after the evaluation")
     p.add_argument("--mesh_resolution", type=int, default=256, help="lattice points per axis of the mesh's volume")
     p.add_argument("--mesh_threshold", type=float, default=10, help="density at which the surface is drawn")
+    # test mode (the reference's --test / --ckpt and its trainer.test, main_nerf.py:188 / :239)
+    p.add_argument("--test", action="store_true", help="test mode: load a checkpoint and write the test frames")
+    p.add_argument("--ckpt", type=str, default="latest",
+                   help="checkpoint --test loads; latest: <workspace>/checkpoints/ngp.pth")
+    p.add_argument("--test_frames", type=int, default=10,
+                   help="steps of the interpolated camera path when the scene has no transforms_test.json")
+    p.add_argument("--write_frames", action="store_true",
+                   help="after training and evaluation, write the test frames to <workspace>/results")
     return p
 
 
@@ -72,6 +86,81 @@ def _eval_split(path):
         if os.path.exists(os.path.join(path, f"transforms_{sp}.json")):
             return sp
     return "train"  # one transforms.json: the training views themselves
+
+
+def _test_path(opt, train, dev, data_args):
+    """The cameras of the test frames -> (poses [n, 4, 4], H, W, intrinsics,
+    what they are): the test split's, or the reference's interpolation
+    (provider.py:208-222) between two training poses drawn with --seed."""
+    import numpy as np
+
+    from nerf.provider import NeRFDataset, interpolate_poses
+    # (NeRFDataset reads the splits only where there is no transforms.json)
+    if not os.path.exists(os.path.join(opt.path, "transforms.json")) and \
+            os.path.exists(os.path.join(opt.path, "transforms_test.json")):
+        test = NeRFDataset(opt.path, dev, type="test", num_rays=opt.num_rays, **data_args)
+        return test.poses, test.H, test.W, test.intrinsics, "test poses"
+    if train is None:  # --test: only the interpolated path needs the training views
+        train = NeRFDataset(opt.path, dev, type="train", num_rays=opt.num_rays, **data_args)
+    n = int(train.poses.shape[0])
+    if n < 2 or opt.test_frames < 1:
+        sys.exit(f"[main_nerf] no transforms_test.json under {opt.path}: a camera path needs two training poses "
+                 f"(the scene has {n}) and --test_frames >= 1 (got {opt.test_frames})")
+    a, b = np.random.default_rng(opt.seed).choice(n, 2, replace=False)
+    poses = interpolate_poses(train.poses[a].cpu().numpy(), train.poses[b].cpu().numpy(), opt.test_frames)
+    return poses, train.H, train.W, train.intrinsics, f"poses between training views {a} and {b}"
+
+
+def _write_test_frames(opt, model, train, dev, data_args):
+    """trainer.test (nerf/utils.py:743-796): every test pose rendered in eval
+    mode on a white background, written under <workspace>/results."""
+    import torch
+
+    from nerf.frames import FrameRenderer, write_frames
+    poses, H, W, intrinsics, what = _test_path(opt, train, dev, data_args)
+    was_training = model.training
+    model.eval()
+    fr = FrameRenderer(model, H, W, intrinsics, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma, bg_color=1.0)
+    fr.load_weights()
+    fr.capture()
+    fr.set_poses(poses)
+    out_dir = os.path.join(opt.workspace, "results")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    paths = write_frames(fr, out_dir, "ngp")
+    secs = time.perf_counter() - t0
+    model.train(was_training)
+    print(f"[main_nerf] {len(fr)} frames {H}x{W} ({what}) in {secs:.2f} s, {len(fr) / secs:.1f} frames/s, "
+          f"written to {out_dir}")
+    return {"frames": len(fr), "frames_per_second": len(fr) / secs, "results": out_dir, "frame_paths": paths}
+
+
+def _test(opt, dev, bound, data_args):
+    """--test: the model of a checkpoint, its frames and (--save_mesh) its mesh; nothing is trained."""
+    import torch
+
+    from nerf import mesh
+    from nerf.network_ff import NeRFNetwork
+    ckpt = os.path.join(opt.workspace, "checkpoints", "ngp.pth") if opt.ckpt == "latest" else opt.ckpt
+    if not os.path.exists(ckpt):
+        sys.exit(f"[main_nerf] --test: no checkpoint at {ckpt} (train first, or name one with --ckpt)")
+    state = torch.load(ckpt, map_location="cpu", weights_only=False)
+    model = NeRFNetwork(encoding="hashgrid", bound=bound, cuda_ray=True, density_scale=1, min_near=opt.min_near,
+                        density_thresh=opt.density_thresh).to(dev)
+    # the model part of FusedTrainer.load_checkpoint; the renderer marches density_bitfield itself
+    model.load_state_dict(state.get("model", state), strict=False)
+    model.mean_count = state.get("mean_count", model.mean_count)
+    model.mean_density = state.get("mean_density", model.mean_density)
+    print(f"[main_nerf] checkpoint {ckpt} (step {state.get('global_step', '?')})")
+    result = {"checkpoint": ckpt}
+    result.update(_write_test_frames(opt, model, None, dev, data_args))
+    if opt.save_mesh:
+        path = os.path.join(opt.workspace, "meshes", "ngp.ply")
+        nv, nt = mesh.save_mesh(model, path, resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)
+        print(f"[main_nerf] mesh {path}: {nv} vertices, {nt} triangles "
+              f"(resolution {opt.mesh_resolution}, threshold {opt.mesh_threshold:g})")
+        result.update(mesh=path, mesh_vertices=nv, mesh_triangles=nt)
+    return result
 
 
 def main(argv=None):
@@ -90,6 +179,8 @@ def main(argv=None):
     bound = int(opt.bound) if float(opt.bound).is_integer() else opt.bound
     data_args = dict(downscale=opt.downscale, scale=opt.scale, offset=opt.offset, store="uint8",
                      depth_scale=opt.depth_scale)
+    if opt.test:
+        return _test(opt, dev, bound, data_args)
     try:
         train = NeRFDataset(opt.path, dev, type="train", num_rays=opt.num_rays, error_map=opt.error_map,
                             error_map_res=opt.error_map_res, **data_args)
@@ -178,6 +269,8 @@ def main(argv=None):
         print(f"[main_nerf] mesh {path}: {nv} vertices, {nt} triangles "
               f"(resolution {opt.mesh_resolution}, threshold {opt.mesh_threshold:g})")
         result.update(mesh=path, mesh_vertices=nv, mesh_triangles=nt)
+    if opt.write_frames:
+        result.update(_write_test_frames(opt, model, train, dev, data_args))
     return result
 
 

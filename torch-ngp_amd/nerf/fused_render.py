@@ -128,6 +128,22 @@ class FusedRenderer:
             self._iterations()
         self.graph = g
 
+    def run_loop(self):
+        """The loop on initialised rays and state (ngp_render_init, or
+        ngp_frame_begin: nerf/frames.py): replays of the captured graph (eager
+        launches before capture()) until the state says done, one state read
+        per replay."""
+        replays = 0
+        for _ in range(-(-self.max_steps // self.K)):  # each iteration advances step by >= 1
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                self._iterations()
+            replays += 1
+            if self._done():
+                break
+        self.iterations = replays * self.K
+
     @torch.no_grad()
     def render(self, rays_o, rays_d, bg_color=1, perturb=False):
         """rays_o / rays_d [N, 3] (or [1, N, 3]) -> dict(image [N, 3], depth
@@ -146,16 +162,7 @@ class FusedRenderer:
         nat.check(lib.ngp_render_init(self.N, P(self.nears), P(self.alive[0]), P(self.rays_t),
                                       P(self.weights_sum), P(self.depth), P(self.image), P(self.state), s),
                   "render_init")
-        replays = 0
-        for _ in range(-(-self.max_steps // self.K)):  # each iteration advances step by >= 1
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self._iterations()
-            replays += 1
-            if self._done():
-                break
-        self.iterations = replays * self.K
+        self.run_loop()
         ws = self.weights_sum
         image = self.image + (1 - ws).unsqueeze(-1) * bg_color
         depth = torch.clamp(self.depth - self.nears, min=0) / (self.fars - self.nears)

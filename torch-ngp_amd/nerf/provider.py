@@ -26,6 +26,58 @@ def nerf_matrix_to_ngp(pose, scale=0.33, offset=(0, 0, 0)):
         [0, 0, 0, 1]], dtype=np.float32)
 
 
+def _quat_from_matrix(R):
+    """Unit quaternion (w, x, y, z) of a rotation matrix, float64: the branch
+    with the largest divisor (Shepperd), so no case loses digits."""
+    R = np.asarray(R, dtype=np.float64)
+    t = R[0, 0] + R[1, 1] + R[2, 2]
+    k = int(np.argmax([t, R[0, 0], R[1, 1], R[2, 2]]))
+    if k == 0:
+        q = np.array([1 + t, R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    elif k == 1:
+        q = np.array([R[2, 1] - R[1, 2], 1 + 2 * R[0, 0] - t, R[0, 1] + R[1, 0], R[0, 2] + R[2, 0]])
+    elif k == 2:
+        q = np.array([R[0, 2] - R[2, 0], R[0, 1] + R[1, 0], 1 + 2 * R[1, 1] - t, R[1, 2] + R[2, 1]])
+    else:
+        q = np.array([R[1, 0] - R[0, 1], R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], 1 + 2 * R[2, 2] - t])
+    return q / np.linalg.norm(q)
+
+
+def _matrix_from_quat(q):
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def interpolate_poses(pose0, pose1, n):
+    """A camera path between two poses for scenes without a test split, the
+    reference's rule (nerf/provider.py:208-222): for i = 0..n the ratio
+    sin((i / n - 0.5) * pi) * 0.5 + 0.5 (slow at both ends), the rotation
+    slerped along the shorter arc (scipy's Slerp there, quaternions here), the
+    translation interpolated linearly. -> float32 [n + 1, 4, 4]."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"interpolate_poses: n must be >= 1, got {n}")
+    pose0, pose1 = np.asarray(pose0, dtype=np.float64), np.asarray(pose1, dtype=np.float64)
+    q0, q1 = _quat_from_matrix(pose0[:3, :3]), _quat_from_matrix(pose1[:3, :3])
+    dot = float(np.dot(q0, q1))
+    if dot < 0:  # q and -q are one rotation: take the shorter arc
+        q1, dot = -q1, -dot
+    theta = math.acos(min(dot, 1.0))  # half the angle between the rotations
+    out = np.zeros((n + 1, 4, 4), dtype=np.float32)
+    for i in range(n + 1):
+        ratio = math.sin((i / n - 0.5) * math.pi) * 0.5 + 0.5
+        if theta < 1e-6:  # sin(theta) ~ 0: the chord is the arc
+            q = (1 - ratio) * q0 + ratio * q1
+        else:
+            q = (math.sin((1 - ratio) * theta) * q0 + math.sin(ratio * theta) * q1) / math.sin(theta)
+        out[i, :3, :3] = _matrix_from_quat(q / np.linalg.norm(q))
+        out[i, :3, 3] = (1 - ratio) * pose0[:3, 3] + ratio * pose1[:3, 3]
+        out[i, 3, 3] = 1
+    return out
+
+
 def _morton3(x, y, z):
     def expand(v):
         v = (v * 0x00010001) & 0xFF0000FF
