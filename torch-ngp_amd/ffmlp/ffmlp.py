@@ -47,7 +47,8 @@ class _ffmlp_forward(Function):
          calc_grad_inputs) = ctx.dims
         grad_inputs = (torch.empty_like(inputs) if calc_grad_inputs
                        else torch.zeros(1, device=grad.device, dtype=grad.dtype))
-        grad_weights = torch.empty_like(weights)
+        # an empty batch launches nothing and leaves grad_weights unwritten
+        grad_weights = torch.empty_like(weights) if B > 0 else torch.zeros_like(weights)
         _backend.ffmlp_backward(grad, inputs, weights, None, B, input_dim, output_dim, hidden_dim,
                                 num_layers, activation, output_activation, calc_grad_inputs, None,
                                 grad_inputs, grad_weights)
