@@ -990,6 +990,61 @@ int ngp_frame_finish(uint32_t H, uint32_t W, const float* image, const float* we
                      const float* nears, const float* fars, float bg_color, uint8_t* rgb8, uint8_t* depth8,
                      float* image_out, float* depth_out, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Background model (the reference's --bg_radius, nerf/network.py:107-129,  */
+/* 202-217; nerf/renderer.py:272-277): csrc/background.hip, DESIGN.md 15     */
+/* ------------------------------------------------------------------------ */
+
+/* Bytes of the backward's fixed-point scratch (64-bit integers) for a table of
+ * table_values values (entries x 2): [table_values | 3072 weight gradients].
+ * 16-byte aligned; zero it once, the backward leaves it zero. */
+size_t ngp_background_scratch_bytes(uint64_t table_values);
+/* One launch over N rays: sph = ngp_sph_from_ray's coordinates, x = [half(SH
+ * degree 4 of rays_d) (16) | the 2-D hash grid at (sph + 1) / 2, 4 levels x 2
+ * features in the half arithmetic of ngp_grid_encode_forward (8) | 0 (8)],
+ * bg f32 [N, 3] = sigmoid(FFMLP 32 -> 64 -> 3 (x)) with the logits and the
+ * sigmoid rounded to half, as the autograd ops give them under autocast.
+ *   table [entries, 2] fp32 (each value rounded to half on load) or fp16
+ *     (table_dtype NGP_DTYPE_F32 / _F16), offsets i32 [5] on the device, S =
+ *     log2(per_level_scale), H = base_resolution; weights fp16 [64 * 32 + 16 *
+ *     64] in FFMLP's layout, 16-byte aligned.
+ *   Training (rgba f32 [N, 4] non-null): rgba[n] := (rgb * a + 1 * (1 - a), 1)
+ *     in fp32 without contraction, the white-blended target a background model
+ *     trains against (nerf/utils.py:508-517); x_save fp16 [N, 32] and sph_save
+ *     f32 [N, 2] (each nullable) keep x and (sph + 1) / 2 for the backward.
+ *   Inference blend (image f32 [N, 3] and weights_sum f32 [N], both or
+ *     neither): image[p] += (1 - weights_sum[p]) * bg[p].
+ * Null required buffers, radius <= 0, N == 0, num_levels != 4 or level_dim != 2:
+ * NGP_ERR_ARG; an MLP other than input_dim 32, hidden_dim 64, num_layers 2:
+ * NGP_ERR_UNSUPPORTED; both before any device work. */
+int ngp_background_forward(const float* rays_o, const float* rays_d, float radius, uint32_t N, const void* table,
+                           int32_t table_dtype, const int32_t* offsets, uint32_t num_levels, uint32_t level_dim,
+                           float S, uint32_t H, const void* weights, uint32_t input_dim, uint32_t hidden_dim,
+                           uint32_t num_layers, float* bg, float* rgba, void* x_save, float* sph_save, float* image,
+                           const float* weights_sum, void* stream);
+/* Two launches after the composite (which must have written out_image [N, 3]
+ * and out_ws [N]) and before the batch buffers are drawn again. Per ray n,
+ * index = rays[n * 3] (rays null: n),
+ *   g_bg = scale * color_weight * (2 / (3 N)) * (out_image - gt) * (1 - out_ws)
+ * with scale the state's GradScaler scale and gt f32 [N, 4] the blended
+ * target; then through the half sigmoid and both layers (the hidden layer is
+ * recomputed from x_save): dW of both, and the input gradient of the 8 grid
+ * columns, scattered with the bilinear weights at sph_save. Each wave sums dW
+ * over its rays in fp32 MFMA accumulators; every sum across waves is a 64-bit
+ * integer atomic add in fixed point (2^-24) into scratch, so the result does
+ * not depend on the atomics' order (bit-reproducible). The second launch
+ * rounds scratch to fp16 into grad_table [table_values] and grad_weights
+ * [3072] and zeroes scratch. inf_flag gets 1 ORed in when a contribution is
+ * not finite or a sum leaves fp16's range, i.e. whenever a value written to
+ * the gradients is not finite or stands for a sum that was. Argument checks
+ * as the forward's. */
+int ngp_background_backward(const int32_t* rays, uint32_t N, const float* out_image, const float* out_ws,
+                            const float* gt, const float* bg, const void* x_save, const float* sph_save,
+                            const int32_t* offsets, uint32_t num_levels, uint32_t level_dim, float S, uint32_t H,
+                            uint64_t table_values, const void* weights, uint32_t input_dim, uint32_t hidden_dim,
+                            uint32_t num_layers, const void* state, float color_weight, float radius, void* scratch,
+                            void* grad_table, void* grad_weights, int32_t* inf_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,12 @@ SIGNATURES = {
     "ngp_frame_begin": [c_vp, c_u32, c_u32, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_frame_finish": [c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_background_scratch_bytes": [ctypes.c_uint64],
+    "ngp_background_forward": [c_vp, c_vp, c_f32, c_u32, c_vp, c_i32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp, c_u32,
+                               c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_background_backward": [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_u32,
+                                ctypes.c_uint64, c_vp, c_u32, c_u32, c_u32, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp,
+                                c_vp, c_vp],
 }
 _RESTYPES = {
     "ngp_last_error": ctypes.c_char_p,
@@ -203,6 +209,7 @@ _RESTYPES = {
     "ngp_grad_exchange_bins": c_u32,
     "ngp_grad_exchange_words": ctypes.c_uint64,
     "ngp_mesh_workspace_bytes": c_sz,
+    "ngp_background_scratch_bytes": c_sz,
 }
 
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}

@@ -22,6 +22,10 @@ poses where the scene has no transforms_test.json, and writes
 <workspace>/results/ngp_<i>_rgb.png and _depth.png, as the reference's
 trainer.test does (main_nerf.py:188 / :239); --write_frames does the same at
 the end of a training run. The frames are made on the device (nerf/frames.py).
+--bg_radius R > 0 adds the reference's background model (nerf/network.py
+:107-129): what lies outside the box is learned as a colour per direction on
+the sphere of radius R (a 2-D hash grid and a small MLP), trained against the
+white-blended targets, and rendered in the evaluation and the frames.
 
 Not here: patch sampling, --color_space linear, more than one
 image per batch, video files, resuming training from a checkpoint."""
@@ -66,6 +70,8 @@ def get_parser():
                    help="dt_gamma (>=0) for adaptive ray marching. set to 0 to disable")
     p.add_argument("--min_near", type=float, default=0.2, help="minimum near distance for camera")
     p.add_argument("--density_thresh", type=float, default=10, help="threshold for density grid to be occupied")
+    p.add_argument("--bg_radius", type=float, default=-1,
+                   help="if positive, use a background model at sphere(bg_radius)")
     # mesh export (the reference's trainer.save_mesh(resolution=256, threshold=10), main_nerf.py:190 / :241)
     p.add_argument("--save_mesh", action="store_true", help="write <workspace>/meshes/ngp.ply after the evaluation")
     p.add_argument("--mesh_resolution", type=int, default=256, help="lattice points per axis of the mesh's volume")
@@ -146,7 +152,7 @@ def _test(opt, dev, bound, data_args):
         sys.exit(f"[main_nerf] --test: no checkpoint at {ckpt} (train first, or name one with --ckpt)")
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
     model = NeRFNetwork(encoding="hashgrid", bound=bound, cuda_ray=True, density_scale=1, min_near=opt.min_near,
-                        density_thresh=opt.density_thresh).to(dev)
+                        density_thresh=opt.density_thresh, bg_radius=opt.bg_radius).to(dev)
     # the model part of FusedTrainer.load_checkpoint; the renderer marches density_bitfield itself
     model.load_state_dict(state.get("model", state), strict=False)
     model.mean_count = state.get("mean_count", model.mean_count)
@@ -187,7 +193,7 @@ def main(argv=None):
     except ValueError as e:  # e.g. an error map resolution out of range
         sys.exit(f"[main_nerf] {e}")
     model = NeRFNetwork(encoding="hashgrid", bound=bound, cuda_ray=True, density_scale=1, min_near=opt.min_near,
-                        density_thresh=opt.density_thresh).to(dev)
+                        density_thresh=opt.density_thresh, bg_radius=opt.bg_radius).to(dev)
     model.train()
     model.mark_untrained_grid(train.poses, train.intrinsics)
     M = (int(opt.sample_budget) + 127) // 128 * 128
@@ -199,7 +205,10 @@ def main(argv=None):
         sys.exit(f"[main_nerf] {e}")
     print(f"[main_nerf] {train.images.shape[0]} images {train.H}x{train.W}x{train.images.shape[3]} "
           f"({train.images.numel() / 2 ** 20:.0f} MiB uint8), {opt.num_rays} rays/step, sample budget {M}"
-          + (f", error map {opt.error_map_res}x{opt.error_map_res}" if opt.error_map else ""))
+          + (f", error map {opt.error_map_res}x{opt.error_map_res}" if opt.error_map else "")
+          + (f", background model at radius {opt.bg_radius:g} "
+             f"({model.encoder_bg.embeddings.numel() + model.bg_net.weights.numel()} parameters)"
+             if opt.bg_radius > 0 else ""))
 
     every = max(1, int(opt.update_extra_interval))
     log_every = max(every, opt.iters // 20 // every * every)

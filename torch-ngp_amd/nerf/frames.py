@@ -48,6 +48,7 @@ class FrameRenderer:
         self.rgb8 = torch.zeros(self.H, self.W, 3, dtype=torch.uint8, device=self.dev)
         self.depth8 = torch.zeros(self.H, self.W, dtype=torch.uint8, device=self.dev)
         self.image, self.depth = None, None  # the float results of render(..., floats=True)
+        self.loop_image = None  # a model with a background, floats=True: the loop's image before its blend
         self.poses = None
         self._host = None  # frames(): two pinned (rgb, depth) pairs and their events
 
@@ -94,8 +95,16 @@ class FrameRenderer:
         if floats and self.image is None:
             self.image = torch.zeros(r.N, 3, device=self.dev)
             self.depth = torch.zeros(r.N, device=self.dev)
+        bg_color = self.bg_color
+        if r._bg:
+            # the model's background, blended into the loop's image in place (self.loop_image
+            # keeps the image before the blend when floats are asked for); finish then adds 0
+            if floats:
+                self.loop_image = r.image.clone()
+            r.background(blend=True)
+            bg_color = 0.0
         nat.check(lib.ngp_frame_finish(self.H, self.W, P(r.image), P(r.weights_sum), P(r.depth), P(r.nears),
-                                       P(r.fars), self.bg_color, P(self.rgb8), P(self.depth8),
+                                       P(r.fars), bg_color, P(self.rgb8), P(self.depth8),
                                        P(self.image) if floats else None, P(self.depth) if floats else None, s),
                   "frame_finish")
         return self.rgb8, self.depth8

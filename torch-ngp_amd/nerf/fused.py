@@ -18,7 +18,12 @@ dataset's depth maps and the composite runs its depth form
 (ngp_nerf_composite_loss_depth); the launches are the same.
 On a dataset with an error map (the reference's --error_map, DESIGN.md section
 13) two launches join them: ngp_error_map_select just before the launch that
-draws, ngp_error_map_update just after the composite.
+draws, ngp_error_map_update just after the composite. A model with a background
+(NeRFNetwork(bg_radius > 0), the reference's --bg_radius)
+adds three: ngp_background_forward at the head of the network phase (the model's
+colour of every ray into `bg`, the targets blended on white), and
+ngp_background_backward's two after the composite; its table and MLP weights are
+parameters 3 and 4 of the flat buffers. World 1 only.
 
 Static shapes: N rays per step, M = the sample buffer (mean_count); rows past
 the marcher's sample count are skipped on the device, so a fixed M costs
@@ -183,6 +188,25 @@ class FusedTrainer:
         self.enc = enc
         self.S = float(np.log2(enc.per_level_scale))
         self.sig_net, self.col_net = model.sigma_net, model.color_net
+        # background model (model.bg_radius > 0): one launch between the
+        # draw and the composite, two after it; off: the step below is unchanged
+        self._bg = float(getattr(model, "bg_radius", -1)) > 0
+        if self._bg:
+            if distributed:
+                raise ValueError("FusedTrainer: a background model (bg_radius > 0) trains single-process only: "
+                                 "its gradients are not part of the data-parallel exchange (distributed=True)")
+            eb, bn = model.encoder_bg, model.bg_net
+            if (eb.input_dim, eb.num_levels, eb.level_dim) != (2, 4, 2) or eb.gridtype_id != 0 or eb.align_corners \
+                    or eb.interp_id != 0:
+                raise ValueError("FusedTrainer: the background grid must be the 2-D hash grid of 4 levels x 2 "
+                                 "features (linear, align_corners off)")
+            if (bn.input_dim, bn.hidden_dim, bn.num_layers, bn.padded_output_dim) != (32, 64, 2, 16):
+                raise ValueError("FusedTrainer: the background MLP must be FFMLP 32 -> 64 -> 3 with 2 layers")
+            far = float(dataset.poses[:, :3, 3].detach().float().cpu().norm(dim=1).max())
+            if not far < float(model.bg_radius):
+                raise ValueError(f"FusedTrainer: a training camera lies {far:g} from the origin, outside the "
+                                 f"background sphere (bg_radius {float(model.bg_radius):g}): its rays do not "
+                                 "meet the sphere from inside (the intersection would be NaN)")
 
         def z(*shape, dtype=torch.float32):
             return torch.zeros(*shape, dtype=dtype, device=dev)
@@ -212,6 +236,8 @@ class FusedTrainer:
         # data-parallel step moves the gradient and the forward copy with one
         # collective each
         self.params = [enc.embeddings, self.sig_net.weights, self.col_net.weights]
+        if self._bg:  # (the "rest" section of plan.sections: an fp16 copy of both)
+            self.params += [model.encoder_bg.embeddings, model.bg_net.weights]
         sizes = [p.numel() for p in self.params]
         self.rank = dist.get_rank() if self._dist else 0
         # ZeRO-1 layout (nerf/zero1.py): 8-aligned tensors, a 64-aligned chunk
@@ -274,14 +300,14 @@ class FusedTrainer:
         self.mlp_img = [z(int(nat.lib().ngp_ffmlp_image_bytes(n.input_dim, n.hidden_dim, n.num_layers)),
                           dtype=torch.uint8) for n in nets]
         self._pk = dict(
-            w=_vp_array([nat.ptr(t) for t in self.w_half[1:]]),
+            w=_vp_array([nat.ptr(t) for t in self.w_half[1:3]]),
             ins=(ctypes.c_uint32 * 2)(*[n.input_dim for n in nets]),
             hid=(ctypes.c_uint32 * 2)(*[n.hidden_dim for n in nets]),
             nl=(ctypes.c_uint32 * 2)(*[n.num_layers for n in nets]),
             img=_vp_array([nat.ptr(t) for t in self.mlp_img]),
             ws=_vp_array([nat.ptr(t) for t in self.mlp_ws]),
             B=(ctypes.c_uint32 * 2)(M, M),
-            gw=_vp_array([nat.ptr(g) for g in self.grads[1:]]))
+            gw=_vp_array([nat.ptr(g) for g in self.grads[1:3]]))
         self.state = z(nat.lib().ngp_fused_state_bytes(), dtype=torch.uint8)
         nat.check(nat.lib().ngp_fused_state_init(nat.ptr(self.state), float(init_scale),
                                                  nat.stream_of(self.state)), "fused_state_init")
@@ -413,6 +439,17 @@ class FusedTrainer:
         # (grid backward, MLP dW reduce) into this flag: the optimizer's found-inf
         # flag (world 1) or the data-parallel guard's per-rank flag
         self._inf_flag = nat.lib().ngp_fused_inf_flag(nat.ptr(self.state), int(self.dp))
+        if self._bg:
+            # what the background forward keeps per ray for its backward, the composite's
+            # image and weight sums (the backward's colour gradient), the fixed-point scratch of its sums
+            eb = model.encoder_bg
+            self.bg_x, self.bg_sph = z(N, 32, dtype=h), z(N, 2)
+            self.out_ws = z(N)
+            if self._emap is None:
+                self.out_image = z(N, 3)
+            self.bg_scratch = z(int(nat.lib().ngp_background_scratch_bytes(self.params[3].numel())),
+                                dtype=torch.uint8)
+            self._bg_grid = (eb.num_levels, eb.level_dim, float(np.log2(eb.per_level_scale)), eb.base_resolution)
         # sparse_exchange: the averaged gradient of every rank's batch replaces
         # this rank's after each backward (the optimizer reads the flag above)
         self._xchg = SparseExchange(self.flat_grad, self._inf_flag, self.world, self._nccl) if self.xchg else None
@@ -1012,6 +1049,8 @@ class FusedTrainer:
         grid_args = (e.input_dim, e.level_dim, e.num_levels, self.S, e.base_resolution, e.gridtype_id,
                      int(e.align_corners), e.interp_id, s)
         table, tdt = (self.params[0], _F32) if self.table32 else (self.w_half[0], _F16)
+        if self._bg:
+            self._background_forward()
         if self.dp and self._dp_tail:
             # + the deferred bookkeeping of the shard update (when the head did
             # not run it: batch drawn ahead) and the MLP packs of the gathered weights
@@ -1057,27 +1096,28 @@ class FusedTrainer:
         if live:
             lv = self._live_bufs
         # error-map sampling: the composite also writes its image, which the map's update reads
-        img_out = P(self.out_image) if self._emap is not None else None
+        img_out = P(self.out_image) if self._emap is not None or self._bg else None
+        ws_out = P(self.out_ws) if self._bg else None  # (a background model's backward reads both)
         if self._loss_job is not None:
             # the depth-supervised loss (and its weights): one entry for both row forms
             job = self._loss_job_live if live else self._loss_job
             chk(lib.ngp_nerf_composite_loss_depth(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                                   P(self.rays), M, N, self.T_thresh, float(m.density_scale),
                                                   P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
-                                                  P(self.g_h), img_out, None, P(self.loss_ray), ctypes.byref(job), s),
+                                                  P(self.g_h), img_out, ws_out, P(self.loss_ray), ctypes.byref(job), s),
                 "composite_loss_depth")
         elif live:
             chk(lib.ngp_nerf_composite_loss_live(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                                  P(self.rays), M, N, self.T_thresh, float(m.density_scale),
                                                  P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
-                                                 P(self.g_h), img_out, None, P(self.loss_ray), P(lv["ray_rows"]),
+                                                 P(self.g_h), img_out, ws_out, P(self.loss_ray), P(lv["ray_rows"]),
                                                  P(lv["cnt"]), P(lv["rows"]), P(lv["total"]), s),
                 "composite_loss_live")
         else:
             chk(lib.ngp_nerf_composite_loss(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                             P(self.rays), M, N, self.T_thresh, float(m.density_scale),
                                             P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
-                                            P(self.g_h), img_out, None, P(self.loss_ray), s), "composite_loss")
+                                            P(self.g_h), img_out, ws_out, P(self.loss_ray), s), "composite_loss")
         self._tick("composite_loss")
         if self._emap is not None:
             # each ray's colour error into its cell of the drawn image's map (before the
@@ -1086,6 +1126,8 @@ class FusedTrainer:
                                          img_out, P(self.rgba), 4, P(self.bg), P(self.image_index), P(self.coarse),
                                          s), "error_map_update")
             self._tick("error_map_update")
+        if self._bg:
+            self._background_backward()
         if self._one_bwd:  # both networks' backward in one launch (ngp_nerf_backward)
             timing = P(self.grid_ws) + self._grid_timing_at if self._grid_timing_at else None
             if live:
@@ -1108,6 +1150,35 @@ class FusedTrainer:
         self._grid_backward(lib, P, s, M, cnt, draw, grid_args)
         if self.dp:
             self._guard()
+
+    def _background_forward(self):
+        """The background model's colour of every ray of the batch into `bg`
+        (one launch, training mode: it also replaces each target by its white
+        blend with alpha 1, so the composite, the error map and the depth form
+        need no case for it). Anywhere between the draw and the composite; here
+        at the head of the network phase, after the pending Adam."""
+        m, P = self.model, nat.ptr
+        bn = m.bg_net
+        nat.check(nat.lib().ngp_background_forward(
+            P(self.rays_o), P(self.rays_d), float(m.bg_radius), self.N, P(self.w_half[3]), _F16,
+            P(m.encoder_bg.offsets), *self._bg_grid, P(self.w_half[4]), bn.input_dim, bn.hidden_dim, bn.num_layers,
+            P(self.bg), P(self.rgba), P(self.bg_x), P(self.bg_sph), None, None, nat.stream_of(self.rays_o)),
+            "background_forward")
+        self._tick("background_forward")
+
+    def _background_backward(self):
+        """The background model's gradients (two launches), after the composite
+        wrote out_image / out_ws and before the bin launch draws the next batch
+        over rgba and bg."""
+        m, P = self.model, nat.ptr
+        bn = m.bg_net
+        nat.check(nat.lib().ngp_background_backward(
+            P(self.rays), self.N, P(self.out_image), P(self.out_ws), P(self.rgba), P(self.bg), P(self.bg_x),
+            P(self.bg_sph), P(m.encoder_bg.offsets), *self._bg_grid, self.params[3].numel(), P(self.w_half[4]),
+            bn.input_dim, bn.hidden_dim, bn.num_layers, P(self.state), self.color_loss_weight, float(m.bg_radius),
+            P(self.bg_scratch), P(self.grads[3]), P(self.grads[4]), self._inf_flag, nat.stream_of(self.rays_o)),
+            "background_backward")
+        self._tick("background_backward")
 
     def _mlp_backward_split(self, lib, P, s, M, cnt, img):
         chk, sn, cn = nat.check, self.sig_net, self.col_net
@@ -1649,6 +1720,7 @@ class FusedTrainer:
         if full:
             m1, m2 = self._moments()
             # param indices follow model.get_params: encoder [0], sigma_net [1], encoder_dir [], color_net [2]
+            # (and encoder_bg [3], bg_net [4] of a model with a background)
             opt_state = {}
             for i, (a, p) in enumerate(zip(self._starts, self.params)):
                 n = p.numel()
@@ -1658,12 +1730,14 @@ class FusedTrainer:
             group = {"lr": self.lr * 0.1 ** min(ep / self.iters, 1), "betas": tuple(self.betas), "eps": self.eps,
                      "weight_decay": 0, "amsgrad": False, "maximize": False, "foreach": None,
                      "capturable": False, "differentiable": False, "fused": None, "initial_lr": self.lr}
+            # (a background model: encoder_bg [3], bg_net [4], the reference's two further groups)
+            groups = ([0], [1], [], [2], [3], [4]) if self._bg else ([0], [1], [], [2])
             state["optimizer"] = {"state": opt_state,
-                                  "param_groups": [dict(group, params=ids) for ids in ([0], [1], [], [2])]}
-            lr_now = self.lr * 0.1 ** min(ep / self.iters, 1)
-            state["lr_scheduler"] = {"base_lrs": [self.lr] * 4, "last_epoch": ep, "_step_count": ep + 1,
-                                     "_get_lr_called_within_step": False, "_last_lr": [lr_now] * 4,
-                                     "lr_lambdas": [None] * 4}
+                                  "param_groups": [dict(group, params=ids) for ids in groups]}
+            lr_now, ng = self.lr * 0.1 ** min(ep / self.iters, 1), len(groups)
+            state["lr_scheduler"] = {"base_lrs": [self.lr] * ng, "last_epoch": ep, "_step_count": ep + 1,
+                                     "_get_lr_called_within_step": False, "_last_lr": [lr_now] * ng,
+                                     "lr_lambdas": [None] * ng}
             state["scaler"] = {"scale": scale, "growth_factor": 2.0, "backoff_factor": 0.5,
                                "growth_interval": self.growth_interval, "_growth_tracker": int(si[self._S_GROWTH])}
         return state
@@ -1702,6 +1776,13 @@ class FusedTrainer:
             si[self._S_DRAW] = draw
         if "optimizer" in state:
             st = state["optimizer"]["state"]
+            # with and without a background model the optimizer holds 5 or 3 tensors
+            has_bg = 3 in st or 4 in st
+            if has_bg != self._bg:
+                raise ValueError(f"FusedTrainer.load_checkpoint: the checkpoint's optimizer state holds "
+                                 f"{len(st)} tensors ({'with' if has_bg else 'without'} a background model), this "
+                                 f"trainer's model has {len(self.params)} ({'with' if self._bg else 'without'} one: "
+                                 f"bg_radius {float(getattr(m, 'bg_radius', -1)):g}); load it with model_only=True")
             for i, (a, p) in enumerate(zip(self._starts, self.params)):
                 if i not in st:
                     continue

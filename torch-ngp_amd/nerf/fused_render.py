@@ -67,6 +67,13 @@ class FusedRenderer:
                         hid=(ctypes.c_uint32 * 2)(*[n.hidden_dim for n in nets]),
                         nl=(ctypes.c_uint32 * 2)(*[n.num_layers for n in nets]),
                         img=(ctypes.c_void_p * 2)(*[nat.ptr(t) for t in self.mlp_img]))
+        # a model with a background (bg_radius > 0): its colour of every ray replaces bg_color
+        self._bg = float(getattr(model, "bg_radius", -1)) > 0
+        if self._bg:
+            eb = model.encoder_bg
+            self.bg = z(N, 3)
+            self.w_half_bg = z(model.bg_net.weights.numel(), dtype=h)
+            self._bg_grid = (eb.num_levels, eb.level_dim, float(np.log2(eb.per_level_scale)), eb.base_resolution)
         self.graph = None
         self.iterations = 0  # device iterations of the last render (graph replays x K)
 
@@ -80,6 +87,8 @@ class FusedRenderer:
         with torch.no_grad():
             self.w_half[0].copy_(self.model.sigma_net.weights.detach().reshape(-1))
             self.w_half[1].copy_(self.model.color_net.weights.detach().reshape(-1))
+            if self._bg:
+                self.w_half_bg.copy_(self.model.bg_net.weights.detach().reshape(-1))
         pk = self._pk
         nat.check(nat.lib().ngp_ffmlp_pack(2, pk["w"], pk["ins"], pk["hid"], pk["nl"], pk["img"], self._stream()),
                   "ffmlp_pack")
@@ -144,6 +153,20 @@ class FusedRenderer:
                 break
         self.iterations = replays * self.K
 
+    def background(self, blend=False):
+        """The background model's colour of the rays in the buffers into
+        self.bg (ngp_background_forward, inference mode; the table is read in
+        fp32 and rounded to half on load). blend: also image += (1 -
+        weights_sum) * bg in place, after the loop (nerf/frames.py)."""
+        m, P = self.model, nat.ptr
+        eb, bn = m.encoder_bg, m.bg_net
+        nat.check(nat.lib().ngp_background_forward(
+            P(self.rays_o), P(self.rays_d), float(m.bg_radius), self.N, P(eb.embeddings), _F32, P(eb.offsets),
+            *self._bg_grid, P(self.w_half_bg), bn.input_dim, bn.hidden_dim, bn.num_layers, P(self.bg), None, None,
+            None, P(self.image) if blend else None, P(self.weights_sum) if blend else None, self._stream()),
+            "background_forward")
+        return self.bg
+
     @torch.no_grad()
     def render(self, rays_o, rays_d, bg_color=1, perturb=False):
         """rays_o / rays_d [N, 3] (or [1, N, 3]) -> dict(image [N, 3], depth
@@ -164,6 +187,8 @@ class FusedRenderer:
                   "render_init")
         self.run_loop()
         ws = self.weights_sum
+        if self._bg:  # as run_cuda: the model's colour replaces bg_color
+            bg_color = self.background()
         image = self.image + (1 - ws).unsqueeze(-1) * bg_color
         depth = torch.clamp(self.depth - self.nears, min=0) / (self.fars - self.nears)
         return {"image": image, "depth": depth, "weights_sum": ws.clone()}

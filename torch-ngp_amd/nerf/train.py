@@ -72,7 +72,8 @@ class Trainer:
         images = data["images"]
         B, N, C = images.shape
         if C == 4:
-            bg_color = torch.rand_like(images[..., :3])  # pixel-wise random background
+            # pixel-wise random background; a background model trains against white (utils.py:508)
+            bg_color = 1 if getattr(self.model, "bg_radius", -1) > 0 else torch.rand_like(images[..., :3])
             gt_rgb = images[..., :3] * images[..., 3:] + bg_color * (1 - images[..., 3:])
         else:
             bg_color = 1
