@@ -21,6 +21,7 @@ import functools
 import numpy as np
 
 import oracle
+import ray_cases
 from helpers import box_bitfield, lego_rays
 
 F32 = np.float32
@@ -252,6 +253,10 @@ LOOP_CONFIGS = {
     "a": dict(N=1024, bound=1.0, C=1, dt_gamma=0.0, T_thresh=1e-4, max_steps=1024, bits="box", seed=21, noise=False),
     "b": dict(N=1000, bound=2.0, C=2, dt_gamma=1 / 128, T_thresh=1e-2, max_steps=1024, bits="fox", seed=22, noise=True),
     "c": dict(N=1024, bound=1.0, C=1, dt_gamma=0.0, T_thresh=1e-4, max_steps=24, bits="box", seed=21, noise=False),
+    # rays the Lego ring never produces (tests/ray_cases.py): cameras inside the box, exact zeros in
+    # directions, NaN near or far, rays pointing away from the box and rays that miss it
+    "d": dict(N=320, bound=2.0, C=2, dt_gamma=1 / 128, T_thresh=1e-2, max_steps=1024, bits="random", seed=23, noise=True,
+              families=("interior", "axis", "face", "away", "miss"), min_near=0.05),
 }
 ALIVE, BY_T, RAN_OUT = 0, 1, 2
 GRID_H = 128
@@ -308,12 +313,23 @@ def loop_inputs(name):
     from nerf.provider import fox_bitfield
     cfg = LOOP_CONFIGS[name]
     N, bound = cfg["N"], cfg["bound"]
-    ro, rd = lego_rays(N, seed=cfg["seed"])
-    if bound > 1:
-        ro = ro * F32(bound / 2.0)
+    if "families" in cfg:  # the named ray families of tests/ray_cases.py, concatenated
+        fams = ray_cases.families(bound, np.random.default_rng(cfg["seed"]))
+        ro = np.concatenate([fams[f][0] for f in cfg["families"]])
+        rd = np.concatenate([fams[f][1] for f in cfg["families"]])
+        assert ro.shape[0] == N
+    else:
+        ro, rd = lego_rays(N, seed=cfg["seed"])
+        if bound > 1:
+            ro = ro * F32(bound / 2.0)
     aabb = np.array([-bound] * 3 + [bound] * 3, F32)
-    nears, fars = oracle.near_far_from_aabb(ro, rd, aabb, 0.2)
-    bits = fox_bitfield() if cfg["bits"] == "fox" else box_bitfield(LOOP_BOXES, cascade=cfg["C"], bound=bound, H=GRID_H)
+    nears, fars = oracle.near_far_from_aabb(ro, rd, aabb, cfg.get("min_near", 0.2))
+    if cfg["bits"] == "fox":
+        bits = fox_bitfield()
+    elif cfg["bits"] == "random":  # 30 % of the cells of every cascade, at random
+        bits = ray_cases.bitfield(cfg["C"], GRID_H, 0.3, cfg["seed"])
+    else:
+        bits = box_bitfield(LOOP_BOXES, cascade=cfg["C"], bound=bound, H=GRID_H)
     noises = np.random.default_rng(cfg["seed"] + 100).random(N, dtype=F32) if cfg["noise"] else np.zeros(N, F32)
     return _freeze(dict(cfg, name=name, rays_o=ro, rays_d=rd, aabb=aabb, nears=nears, fars=fars,
                         bits=np.ascontiguousarray(bits), noises=noises))

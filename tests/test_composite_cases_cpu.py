@@ -102,6 +102,30 @@ def test_field_is_exact_and_its_sigmoid_robust():
     assert (to_tie > 8 * np.spacing(exact.astype(np.float32))).all()
 
 
+def test_loop_case_d_holds_the_degenerate_rays():
+    """Configuration d (rays of tests/ray_cases.py) meets every claim below,
+    and on top of them: cameras inside the box, exact zeros in directions, NaN
+    near and NaN far, rays pointing away and rays that miss. The loop starts
+    them all at rays_t = near; those that can take no sample leave in the
+    first iteration without one and without a rays_t."""
+    inp, o = cc.loop_inputs("d"), cc.oracle_loop("d")
+    nears, fars = inp["nears"], inp["fars"]
+    fmax = np.finfo(np.float32).max
+    nan, miss = np.isnan(nears) | np.isnan(fars), fars == fmax
+    away = ~nan & ~miss & (fars < nears)
+    assert np.isnan(nears).sum() >= 2 and np.isnan(fars).sum() >= 2 and miss.sum() >= 64 and away.sum() >= 64
+    assert ((inp["rays_d"] == 0).sum(1) == 2).sum() >= 64 and np.signbit(inp["rays_d"][inp["rays_d"] == 0]).any()
+    assert (np.abs(inp["rays_o"]) <= inp["bound"]).all(1).sum() >= 128
+    dead = nan | miss | away
+    assert (o["death_iter"][dead] == 0).all() and (o["samples"][dead] == 0).all()
+    assert (o["cause"][dead] == cc.RAN_OUT).all()
+    first = o["iters"][0]
+    assert (first["alive_after"][dead] == -1).all()
+    assert np.array_equal(first["rays_t"][dead].view(np.uint32), nears[dead].view(np.uint32))
+    assert (o["samples"][~dead] > 0).sum() >= 100
+    assert (o["death_iter"] > 0).sum() >= 100  # the loop goes on past the first iteration for the rest
+
+
 @pytest.mark.parametrize("name", sorted(cc.LOOP_CONFIGS))
 def test_loop_cases_cover_both_endings(name):
     inp, o = cc.loop_inputs(name), cc.oracle_loop(name)
