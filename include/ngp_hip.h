@@ -600,7 +600,11 @@ int ngp_nerf_sigma_forward(const void* inputs, const void* weights, const void* 
  * network on pair-major encodings enc [16][B][2] (rows < *count), the
  * ngp_nerf_sigma_forward epilogue (h_out, sigma, color_in, same values), and
  * the colour network on color_in, rgb logits color_out [B,16] half. Images:
- * the two networks' ngp_ffmlp_pack images. 64-wide networks with 32 inputs. */
+ * the two networks' ngp_ffmlp_pack images. 64-wide networks with 32 inputs,
+ * num_layers 2..3 (sigma) and 2..4 (colour). No clamp in the forward: sigma is
+ * inf where exp(h[:,0]) overflows fp32. All six depth pairs are held to the
+ * float64 oracle and to the two launches in tests/test_gpu_nerf_net.py (cases
+ * a, b); the default 2 / 3 also in tests/test_gpu_e2e_oracle.py. */
 int ngp_nerf_forward(const void* enc, const void* sigma_image, const void* color_image, uint32_t B,
                      const int32_t* count, uint32_t hidden_dim, uint32_t num_layers,
                      uint32_t hidden_dim_color, uint32_t num_layers_color, void* h_out, float* sigma,
@@ -624,6 +628,11 @@ int ngp_ffmlp_backward_rows(const void* grad, const void* inputs, const void* we
  * gradient g_enc): the input gradients bit for bit, the dW partials summed in
  * another order. Workspaces as ngp_ffmlp_backward_workspace_bytes of each
  * network; reduce with ngp_ffmlp_reduce. 64-wide networks, num_layers 2..3.
+ * Rows at or past *count contribute nothing and keep their g_h / g_enc; with
+ * *count <= 0 every workgroup still writes its (zero) dW partial. All four
+ * depth pairs, here and in ngp_nerf_backward_live, are held to the float64
+ * oracle and to the two calls in tests/test_gpu_nerf_net.py (cases c, d); the
+ * default 2 / 3 also in tests/test_gpu_fused.py and tests/test_gpu_e2e_oracle.py.
  * timing (nullable): the grid backward's NGP_GRID_TIMING ring (the fused grid
  * workspace at ngp_grid_encode_backward_fused_timing_offset): workgroup b's
  * end goes into end slot NGP_GRID_TIMING_MAX_WG - 1 - b of the next call, and
@@ -635,7 +644,10 @@ int ngp_nerf_backward(const void* g_color_out, const void* color_in, const void*
                       void* color_workspace, size_t color_workspace_bytes, uint32_t* timing, void* stream);
 /* ngp_nerf_backward over the rows live_rows[0 .. *live_count) only (see
  * ngp_nerf_composite_loss_live): input gradients are written for those rows,
- * the others are left as they were. */
+ * the others are left as they were (and their inputs are not read). Only the
+ * first ngp_reduce::live_slab_rows workgroups write a dW partial: a caller
+ * that reduces with ngp_ffmlp_reduce, which takes no live count, zeroes the
+ * workspaces first. */
 int ngp_nerf_backward_live(const void* g_color_out, const void* color_in, const void* color_image, void* g_h,
                            const void* enc, const void* sigma_image, void* g_enc, uint32_t B,
                            const int32_t* live_rows, const int32_t* live_count, uint32_t hidden_dim,
@@ -857,7 +869,11 @@ int ngp_density_grid_points_sorted(const int32_t* coords, const float* noise, ui
  * density = exp(h[:,0]) * density_scale (renderer.py:535-536), written as a
  * max into tmp_grid[indices[b]] (tmp_grid f32 [C * H^3], -1 where unset;
  * a cell drawn twice keeps the larger density). image: ngp_ffmlp_pack image
- * of the network or NULL. */
+ * of the network or NULL. With an image and in_dim 32 the streaming kernel
+ * runs (hidden 32 / 64, num_layers 2..4); every other shape of the FFMLP, and
+ * a NULL image, takes the generic kernel. tests/test_gpu_nerf_net.py (case f)
+ * holds both, and ngp_nerf_density_forward_rows, to the float64 oracle on all
+ * of these shapes; the trainer's 64 / 2 also in tests/test_gpu_density.py. */
 int ngp_nerf_density_forward(const void* inputs, const void* weights, const void* image, uint32_t B,
                              uint32_t in_dim, uint32_t hidden_dim, uint32_t num_layers, float density_scale,
                              const int32_t* indices, float* tmp_grid, void* stream);

@@ -1292,9 +1292,14 @@ template <int NHS, int NHC>
 struct NerfBwdLds {
     using LC = BwdLds<64, 1, NHC>;
     using LS = BwdLds<64, 1, NHS>;
-    static constexpr size_t sigma_frags = LC::total;  // the sigma image's offset
+    // what the sigma pass lays over the colour pass's space: its tiles and
+    // its two fold images (its fragments stay where they were copied)
+    static constexpr size_t sigma_overlay = LS::tile_bytes > 2 * LS::acc_bytes ? LS::tile_bytes : 2 * LS::acc_bytes;
+    // the sigma image's offset: past the colour pass and past that overlay (a
+    // 3-layer sigma network beside a 2-layer colour network needs the latter)
+    static constexpr size_t sigma_frags = LC::total > sigma_overlay ? LC::total : sigma_overlay;
     static constexpr size_t total = sigma_frags + LS::frag_bytes;
-    static constexpr bool fits = total <= 160 * 1024 && LS::total <= sigma_frags;
+    static constexpr bool fits = total <= 160 * 1024;
 };
 template <int NHS, int NHC>
 __global__ void __launch_bounds__(kBwdThreads)
@@ -1442,7 +1447,10 @@ int launch_fwd_nerf(const void* in, const void* w, const void* image, uint32_t B
 template <int W, int IN_KS, int NH>
 int launch_fwd_density(const void* in, const void* w, const void* image, uint32_t B, uint32_t in_dim,
                        const EpiDensity& epi, hipStream_t st) {
-    if (IN_KS == 1 && image) {  // the streaming kernel (prepacked image, 32 inputs)
+    // the streaming kernel (prepacked image, 32 inputs). It reads 16 pairs per
+    // row whatever in_dim says, so a 16-wide input (also IN_KS == 1) keeps the
+    // generic kernel, whose loader masks the columns past in_dim
+    if (IN_KS == 1 && in_dim == 32 && image) {
         using N = Net<W, 1, NH>;
         const size_t lds = (size_t)N::FWD_FRAGS * 64 * 16;
         // the workgroups resident at once (occupancy x CUs, queried once per
@@ -1571,15 +1579,13 @@ int launch_bwd(const void* grad, const void* in, const void* w, const void* imag
 
 template <int NHS, int NHC>
 int launch_nerf_bwd(const NerfBwdArgs& a, hipStream_t st) {
-    if constexpr (!NerfBwdLds<NHS, NHC>::fits) {
-        return ngp_set_error(NGP_ERR_UNSUPPORTED, "nerf_backward: networks too large for one launch's LDS");
-    } else {
-        const uint32_t blocks = bwd_blocks(a.B);
-        if (blocks == 0) return NGP_OK;
-        constexpr size_t lds_bytes = NerfBwdLds<NHS, NHC>::total;
-        hipLaunchKernelGGL((k_nerf_bwd<NHS, NHC>), dim3(blocks), dim3(kBwdThreads), lds_bytes, st, a);
-        return ngp_check_launch("nerf_backward");
-    }
+    // all four depth pairs nerf_backward_impl dispatches fit (134 KB at most)
+    static_assert(NerfBwdLds<NHS, NHC>::fits, "nerf backward LDS budget exceeded");
+    const uint32_t blocks = bwd_blocks(a.B);
+    if (blocks == 0) return NGP_OK;
+    constexpr size_t lds_bytes = NerfBwdLds<NHS, NHC>::total;
+    hipLaunchKernelGGL((k_nerf_bwd<NHS, NHC>), dim3(blocks), dim3(kBwdThreads), lds_bytes, st, a);
+    return ngp_check_launch("nerf_backward");
 }
 
 #define MLP_DISPATCH(FN, ...)                                                              \
