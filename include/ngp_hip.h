@@ -654,6 +654,58 @@ int ngp_nerf_backward_live(const void* g_color_out, const void* color_in, const 
                            uint32_t num_layers, uint32_t hidden_dim_color, uint32_t num_layers_color,
                            void* sigma_workspace, size_t sigma_workspace_bytes, void* color_workspace,
                            size_t color_workspace_bytes, uint32_t* timing, void* stream);
+/* ngp_nerf_backward_live with a light regime for few live rows. With
+ * 0 < *live_count <= min(dw_rows_max, whole 32-row chunks of dw_stash_rows,
+ * 32 rows per workgroup of the launch: ceil(ceil(B / 32) / 4), at most 256)
+ * the launch forms no dW: it writes g_h[:, 1:16] and g_enc exactly as
+ * ngp_nerf_backward_live does (bit for bit) and stashes, per 32-row chunk and
+ * transposed, the operands of the dW products (output gradients, inputs,
+ * hidden post-activations and deltas; rows of the last chunk past the count
+ * as zeros) in dw_stash (ngp_nerf_dw_stash_bytes(dw_stash_rows, ..) bytes,
+ * scratch: nothing is read from it), and leaves the workspaces untouched. The
+ * weight gradients are then formed from the stash, summed in fp32 in the slab
+ * path's own order (one chunk per workgroup: the same bits as
+ * ngp_nerf_backward_live + ngp_ffmlp_reduce), by
+ * ngp_nerf_dw_reduce or by the bin launch of
+ * ngp_grid_encode_backward_fused_dw_batch_live, called with the same stash,
+ * rows and dw_rows_max. With more rows, or dw_rows_max 0, the launch is
+ * ngp_nerf_backward_live's, dW partials included, and those two calls reduce
+ * them as ngp_ffmlp_reduce does: every output bit-identical. The regime is
+ * chosen on the device from *live_count. tests/test_gpu_nerf_dw.py. */
+size_t ngp_nerf_dw_stash_bytes(uint32_t rows, uint32_t num_layers, uint32_t num_layers_color);
+int ngp_nerf_backward_live_dw(const void* g_color_out, const void* color_in, const void* color_image, void* g_h,
+                              const void* enc, const void* sigma_image, void* g_enc, uint32_t B,
+                              const int32_t* live_rows, const int32_t* live_count, uint32_t hidden_dim,
+                              uint32_t num_layers, uint32_t hidden_dim_color, uint32_t num_layers_color,
+                              void* sigma_workspace, size_t sigma_workspace_bytes, void* color_workspace,
+                              size_t color_workspace_bytes, uint32_t* timing, void* dw_stash,
+                              uint32_t dw_stash_rows, uint32_t dw_rows_max, void* stream);
+/* The weight gradients (fp16) of ngp_nerf_backward_live_dw in one launch:
+ * network 0 the sigma network, 1 the colour network (workspaces, Bs = the
+ * backward's B twice, shapes and grad_weights as ngp_ffmlp_reduce lists them).
+ * Light regime: the products from the stash (exact zeros with
+ * *live_count <= 0); otherwise the slab reduce over the live rows' slab rows.
+ * nonfinite (nullable): set to 1 when a written grad is inf/nan. */
+int ngp_nerf_dw_reduce(void* const* workspaces, const uint32_t* Bs, const uint32_t* in_dims,
+                       const uint32_t* hidden_dims, const uint32_t* num_layers, void* const* grad_weights,
+                       int32_t* nonfinite, const int32_t* live_count, const void* dw_stash,
+                       uint32_t dw_stash_rows, uint32_t dw_rows_max, void* stream);
+/* ngp_grid_encode_backward_fused_reduce_batch_live (src null) or
+ * .._reduce_batch_images (src given, live_rows required here) after
+ * ngp_nerf_backward_live_dw: in the light regime the first workgroups of the
+ * bin launch's slab-reduce column, one per 16x16 tile of the two networks'
+ * dW, form the weight gradients from the stash (ngp_nerf_dw_reduce's values
+ * bit for bit) and the column's other workgroups return at once; in the other
+ * regime the column is the slab reduce, the launch that of
+ * .._reduce_batch_live. n_nets 2: sigma, colour. */
+int ngp_grid_encode_backward_fused_dw_batch_live(
+    const void* grad, const float* xyz, float bound, const int32_t* offsets, void* grad_embeddings, uint32_t B,
+    const int32_t* live_rows, const int32_t* live_count, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+    uint32_t gridtype, int32_t align_corners, uint32_t interp, const int32_t* offsets_host, void* workspace,
+    size_t workspace_bytes, int32_t grad_layout, int32_t* nonfinite, int32_t n_nets, void* const* mlp_workspaces,
+    const uint32_t* mlp_Bs, const uint32_t* in_dims, const uint32_t* hidden_dims, const uint32_t* num_layers,
+    void* const* grad_weights, int32_t* mlp_nonfinite, const ngp_batch_job* job, const ngp_image_source* src,
+    const void* dw_stash, uint32_t dw_stash_rows, uint32_t dw_rows_max, void* stream);
 /* Sums the deferred dW partials of n backward calls (same B and shapes as
  * those calls) into grad_weights[k], in one launch (n <= 4). nonfinite
  * (nullable): set to 1 when a written grad is inf/nan (GradScaler's check). */

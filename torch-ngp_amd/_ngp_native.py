@@ -141,6 +141,14 @@ SIGNATURES = {
                                                            c_u32, c_u32, c_u32, c_f32, c_u32, c_u32, c_i32, c_u32,
                                                            c_vp, c_vp, c_sz, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp,
                                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_nerf_dw_stash_bytes": [c_u32, c_u32, c_u32],
+    "ngp_nerf_backward_live_dw": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_u32, c_u32,
+                                  c_u32, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_u32, c_u32, c_vp],
+    "ngp_nerf_dw_reduce": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp],
+    "ngp_grid_encode_backward_fused_dw_batch_live": [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_vp, c_vp,
+                                                     c_u32, c_u32, c_u32, c_f32, c_u32, c_u32, c_i32, c_u32,
+                                                     c_vp, c_vp, c_sz, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp],
     "ngp_nerf_glue_forward": [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_vp, c_vp],
     "ngp_nerf_glue_backward": [c_vp, c_vp, c_u32, c_vp, c_vp],
     "ngp_nerf_composite_loss": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
@@ -203,6 +211,7 @@ _RESTYPES = {
     "ngp_render_count": c_vp,
     "ngp_grid_encode_backward_fused_workspace_bytes": c_sz,
     "ngp_ffmlp_image_bytes": c_sz,
+    "ngp_nerf_dw_stash_bytes": c_sz,
     "ngp_density_grid_draw_workspace_bytes": c_sz,
     "ngp_density_grid_sort_workspace_bytes": c_sz,
     "ngp_density_grid_ostat_workspace_bytes": c_sz,

@@ -27,6 +27,7 @@
 #include "ngp_reduce.h"
 #include "sh_basis.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -835,6 +836,45 @@ NGP_DEV void dw_accum(const ngp_half* __restrict__ dT, const ngp_half* __restric
         for (int n = 0; n < MI; ++n) acc[m][n] = mfma(a[m], b[n], acc[m][n]);
 }
 
+// The light regime (ngp_nerf_backward_live_dw): instead of a dW product, the
+// operand a wave has just stored in its transposing tile goes to the chunk's
+// stash record, transposed ([unit][32 rows], ngp_reduce.h): lane (g, c) of
+// read_tr(tile, m) holds 8 rows of unit 16m + c, one 16-byte store (a
+// wave's store covers 16 units' 1 KB). A half chunk (HALF: 16 rows in the
+// tile's rows 0..15) stores the low 4 rows of each lane only, at slot
+// 8g + 4 half: the chunk's two halves, two waves, fill the record between them.
+// Both operands of a product are stashed by the same rule, so K slot j of a
+// record holds the same row in both.
+struct DwStash {
+    ngp_half* rec;  // the chunk's record (null outside the light regime)
+    uint32_t half;  // HALF: which half of the chunk (0 / 1)
+};
+template <int MT, bool HALF>
+NGP_DEV void stash_tiles(const ngp_half* __restrict__ tile, const DwStash& st, uint32_t unit0) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+    asm volatile("" ::: "memory");  // as dw_accum: after the wave's own tile stores
+    if constexpr (HALF) {
+        const int q = (lane >> 2) & 3, p = lane & 3;
+        short4v v[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+            v[m] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                (__attribute__((address_space(3))) short4v*)(tile + (4 * g + q) * kTileLd + 16 * m + 4 * p));
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+            *reinterpret_cast<short4v*>(st.rec + (size_t)(unit0 + 16 * m + c) * 32 + 8 * g + 4 * st.half) = v[m];
+    } else {
+        half8 v[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) v[m] = read_tr(tile, m);
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+            *reinterpret_cast<half8*>(st.rec + (size_t)(unit0 + 16 * m + c) * 32 + 8 * g) = v[m];
+    }
+}
+
 // delta (C layout, MT tiles) * act'(post-activation h, permuted B form) -> permuted B form
 template <int MT, int KS, typename ACT, int NB>
 NGP_DEV void pack_delta(const f32x4 (&acc)[NB][MT], const half8 (&h)[NB][KS], ACT act,
@@ -1033,12 +1073,18 @@ struct NoIdle {
     NGP_DEV void operator()() const {}
 };
 
-template <int W, int IN_KS, int NH, bool GI_SYNC, typename FA, typename XL, typename GI, typename MAP, typename PRE,
-          typename HALF = NoHalf, typename IDLE = NoIdle>
+// LIGHT (the NeRF backward's light regime, k_nerf_bwd): no dW at all. The
+// wave stashes each product's operands per chunk instead (stash_tiles; stash:
+// this network's first unit of chunk 0's record, rec_halves: halves per chunk
+// record), there is no fold and no slab row, and the pass ends at the one
+// barrier (GI_SYNC) that publishes its input gradients to the workgroup.
+template <int W, int IN_KS, int NH, bool GI_SYNC, bool LIGHT, typename FA, typename XL, typename GI, typename MAP,
+          typename PRE, typename HALF = NoHalf, typename IDLE = NoIdle>
 NGP_DEV void bwd_phase(const half8* __restrict__ fr, ngp_half* __restrict__ tiles, float* __restrict__ img_base,
                        const ngp_half* __restrict__ grad, const ngp_half* __restrict__ inputs, XL xl, GI gi_out,
                        bool want_gi, float* __restrict__ slab, uint32_t nparams, uint32_t B, uint32_t in_dim,
-                       FA act, MAP map, PRE pre, HALF half = HALF{}, IDLE idle = IDLE{}) {
+                       FA act, MAP map, PRE pre, HALF half = HALF{}, IDLE idle = IDLE{},
+                       ngp_half* __restrict__ stash = nullptr, uint32_t rec_halves = 0) {
     using N = Net<W, IN_KS, NH>;
     constexpr int LAST = N::NMAT - 1;
     MSTAMP(0);
@@ -1086,10 +1132,25 @@ NGP_DEV void bwd_phase(const half8* __restrict__ fr, ngp_half* __restrict__ tile
         // round trip (LDS executes one wave's operations in order, the reads
         // see the stores).
         // last matmul: dW += dout^T . h[NH]
+        // LIGHT: the same tiles, read back transposed and stashed (record
+        // layout: ngp_reduce.h) where the dW product stood
+        constexpr bool HM = NBC == 1;
+        constexpr uint32_t U_H = 48, U_D = 48 + 64 * (NH + 1);
+        DwStash st{nullptr, 0u};
+        if constexpr (LIGHT) {
+            static_assert(W == 64 && IN_KS == 1, "the stash record is laid out for the NeRF networks");
+            st.rec = stash + (size_t)(row0 / (16 * kNB)) * rec_halves;
+            st.half = (row0 / 16) & 1u;
+        }
         write_rows<1, false>(dT, dout, kOut);
         write_rows<N::KSW, true>(hT, h[NH], W);
         dense<N::MTW, 1>(fr, bwd_desc<W, IN_KS, NH>(LAST, in_dim).frag0 + N::FWD_FRAGS, dout, a);
-        dw_accum<1, N::MTW>(dT, hT, dw_last);
+        if constexpr (LIGHT) {
+            stash_tiles<1, HM>(dT, st, 0u);
+            stash_tiles<N::MTW, HM>(hT, st, U_H + 64 * NH);
+        } else {
+            dw_accum<1, N::MTW>(dT, hT, dw_last);
+        }
         half8 d[NBC][N::KSW];  // delta of a matmul's pre-activation output, permuted B form
         pack_delta<N::MTW, N::KSW>(a, h[NH], act, d);
 #pragma unroll
@@ -1097,7 +1158,12 @@ NGP_DEV void bwd_phase(const half8* __restrict__ fr, ngp_half* __restrict__ tile
             write_rows<N::KSW, true>(dT, d, W);
             write_rows<N::KSW, true>(hT, h[q - 1], W);
             dense<N::MTW, N::KSW>(fr, bwd_desc<W, IN_KS, NH>(q, in_dim).frag0 + N::FWD_FRAGS, d, a);
-            dw_accum<N::MTW, N::MTW>(dT, hT, dw_hid[q - 1]);
+            if constexpr (LIGHT) {
+                stash_tiles<N::MTW, HM>(dT, st, U_D + 64 * q);
+                stash_tiles<N::MTW, HM>(hT, st, U_H + 64 * (q - 1));
+            } else {
+                dw_accum<N::MTW, N::MTW>(dT, hT, dw_hid[q - 1]);
+            }
             pack_delta<N::MTW, N::KSW>(a, h[q - 1], act, d);
         }
         // first matmul: dW += d^T . x, and grad_inputs = W_0^T d
@@ -1105,7 +1171,12 @@ NGP_DEV void bwd_phase(const half8* __restrict__ fr, ngp_half* __restrict__ tile
         write_rows<IN_KS, false>(hT, x, in_dim);
         f32x4 gi[NBC][N::IN_MT];
         if (want_gi) dense<N::IN_MT, N::KSW>(fr, bwd_desc<W, IN_KS, NH>(0, in_dim).frag0 + N::FWD_FRAGS, d, gi);
-        dw_accum<N::MTW, N::IN_MT>(dT, hT, dw_first);
+        if constexpr (LIGHT) {
+            stash_tiles<N::MTW, HM>(dT, st, U_D);
+            stash_tiles<N::IN_MT, HM>(hT, st, 16u);
+        } else {
+            dw_accum<N::MTW, N::IN_MT>(dT, hT, dw_first);
+        }
         if (want_gi) gi_out(row0, B, in_dim, gi);
     };
 
@@ -1141,16 +1212,24 @@ NGP_DEV void bwd_phase(const half8* __restrict__ fr, ngp_half* __restrict__ tile
             load_rows<1>(grad, kOut, hrow, B, d1, xl.map);
         }
         asm volatile("" ::: "memory");  // after the last chunk's transposed reads
-        const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-        const uint32_t lane = threadIdx.x & 63;
-        for (uint32_t i = lane; i < 16 * kTileLd / 8; i += 64) {
-            reinterpret_cast<half8*>(dT + 16 * kTileLd)[i] = z;
-            reinterpret_cast<half8*>(hT + 16 * kTileLd)[i] = z;
+        if constexpr (!LIGHT) {  // (the light regime's half stash reads rows 0..15 only)
+            const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+            const uint32_t lane = threadIdx.x & 63;
+            for (uint32_t i = lane; i < 16 * kTileLd / 8; i += 64) {
+                reinterpret_cast<half8*>(dT + 16 * kTileLd)[i] = z;
+                reinterpret_cast<half8*>(hT + 16 * kTileLd)[i] = z;
+            }
         }
         asm volatile("" ::: "memory");
         body(std::integral_constant<int, 1>{}, hrow, x1, d1);
     }
     MSTAMP(12);
+    if constexpr (LIGHT) {
+        if (nst == 0 && hrow == kNoHalf) idle();  // a wave without rows (wave-uniform)
+        if constexpr (GI_SYNC) __syncthreads();   // the waves' input-gradient stores, for the next pass
+        MSTAMP(14);
+        return;
+    }
     // fold the waves' register tiles into two LDS dW images (round r: waves
     // 2r and 2r + 1 store (r = 0) or add into images 0 and 1), then publish
     // image0 + image1 as the slab row: a fixed summation order, so dW is
@@ -1246,7 +1325,7 @@ k_mlp_bwd(const ngp_half* __restrict__ grad, const ngp_half* __restrict__ inputs
     extern __shared__ half8 lds[];
     ngp_half* tiles = reinterpret_cast<ngp_half*>(reinterpret_cast<char*>(lds) + L::frag_bytes);
     const uint32_t stride = gridDim.x * kBwdWaves, c0 = blockIdx.x * kBwdWaves + (threadIdx.x >> 6);
-    bwd_phase<W, IN_KS, NH, false>(lds, tiles, reinterpret_cast<float*>(lds), grad, inputs, xl, gi_out, want_gi, slab,
+    bwd_phase<W, IN_KS, NH, false, false>(lds, tiles, reinterpret_cast<float*>(lds), grad, inputs, xl, gi_out, want_gi, slab,
                             nparams, B, in_dim, act, [=](uint32_t k) { return c0 + k * stride; },
                             [&]() {
                                 copy_frags<L::FRAGS, kBwdThreads>(lds, image);
@@ -1286,6 +1365,12 @@ struct NerfBwdArgs {
     // where this launch ended. Plain stores: one contended atomic per
     // workgroup cost ~2 us at the launch's end.
     uint32_t* timing;
+    // the light regime (k_nerf_bwd<.., true>, ngp_nerf_backward_live_dw): with a
+    // row list and 0 < *count <= dw_rows_max no dW is formed; the dW products'
+    // operands go to the stash instead (ngp_reduce.h), for the product column
+    // of the next bin launch
+    ngp_half* stash;
+    uint32_t dw_rows_max;
 };
 
 template <int NHS, int NHC>
@@ -1301,7 +1386,7 @@ struct NerfBwdLds {
     static constexpr size_t total = sigma_frags + LS::frag_bytes;
     static constexpr bool fits = total <= 160 * 1024;
 };
-template <int NHS, int NHC>
+template <int NHS, int NHC, bool DW>
 __global__ void __launch_bounds__(kBwdThreads)
 k_nerf_bwd(NerfBwdArgs a) {
     using LC = BwdLds<64, 1, NHC>;
@@ -1332,29 +1417,54 @@ k_nerf_bwd(NerfBwdArgs a) {
     // image meanwhile, off the colour pass's critical path
     const bool idle_copy = n == 1 || n == 3;
     const uint32_t idle0 = n == 1 ? 2u : 3u;
+    auto pre_of = [&]() {
+        return [&]() {
+            copy_frags<LC::FRAGS, kBwdThreads>(lds, a.color_image);
+            if (!idle_copy) copy_frags<LS::FRAGS, kBwdThreads>(sfr, a.sigma_image);
+            __syncthreads();
+        };
+    };
+    auto idle_of = [&]() {
+        return [&]() {  // the colour pass's idle waves copy the sigma image (done by the pass's barrier)
+            if (idle_copy)
+                copy_frags_part<LS::FRAGS>(sfr, a.sigma_image, threadIdx.x - idle0 * 64, (kBwdWaves - idle0) * 64);
+        };
+    };
+    // The light regime (launch-uniform: every workgroup reads the same count):
+    // the same chunk dealing, recompute, delta chain and input-gradient stores
+    // (bit-identical g_h and g_enc), the dW operands stashed per chunk, one
+    // barrier between the passes. The workgroups without a chunk leave.
+    bool light = false;
+    if constexpr (DW) light = a.rows && a.dw_rows_max && B <= a.dw_rows_max;
+    if constexpr (DW) if (light) {
+        if (b < nch) {
+            constexpr uint32_t REC = (ngp_reduce::dw_net_units(NHC) + ngp_reduce::dw_net_units(NHS)) * 32u;
+            bwd_phase<64, 1, NHC, true, true>(
+                lds, reinterpret_cast<ngp_half*>(reinterpret_cast<char*>(lds) + LC::frag_bytes),
+                reinterpret_cast<float*>(lds), a.g_color_out, a.color_in, InRowMajor{a.rows},
+                GiNerfGeo{a.g_h, a.rows}, true, nullptr, 0u, B, 32u, ActReLU{}, map_of(w), pre_of(), half_of(w),
+                idle_of(), a.stash, REC);
+            bwd_phase<64, 1, NHS, false, true>(
+                sfr, reinterpret_cast<ngp_half*>(lds), reinterpret_cast<float*>(lds), a.g_h, a.enc,
+                InPairMajor{a.B, a.rows}, GiPairMajor{a.g_enc, a.B, a.rows}, true, nullptr, 0u, B, 32u, ActReLU{},
+                map_of(kBwdWaves - 1 - w), []() {}, half_of(kBwdWaves - 1 - w), NoIdle{},
+                a.stash + (size_t)ngp_reduce::dw_net_units(NHC) * 32u, REC);
+        }
+    }
     // live rows: the workgroups past the slab rows the reduce reads have no
     // chunk and skip both passes (ngp_reduce::live_slab_rows)
-    if (!a.rows || b < ngp_reduce::live_slab_rows((int32_t)B, G)) {
-    bwd_phase<64, 1, NHC, true>(lds, reinterpret_cast<ngp_half*>(reinterpret_cast<char*>(lds) + LC::frag_bytes),
+    if (!light && (!a.rows || b < ngp_reduce::live_slab_rows((int32_t)B, G))) {
+    bwd_phase<64, 1, NHC, true, false>(lds, reinterpret_cast<ngp_half*>(reinterpret_cast<char*>(lds) + LC::frag_bytes),
                           reinterpret_cast<float*>(lds), a.g_color_out, a.color_in, InRowMajor{a.rows},
                           GiNerfGeo{a.g_h, a.rows},
-                          true, a.slab_color, a.np_color, B, 32u, ActReLU{}, map_of(w),
-                          [&]() {
-                              copy_frags<LC::FRAGS, kBwdThreads>(lds, a.color_image);
-                              if (!idle_copy) copy_frags<LS::FRAGS, kBwdThreads>(sfr, a.sigma_image);
-                              __syncthreads();
-                          }, half_of(w),
-                          [&]() {  // the colour pass's idle waves copy the sigma image (done by the fold's barrier)
-                              if (idle_copy)
-                                  copy_frags_part<LS::FRAGS>(sfr, a.sigma_image, threadIdx.x - idle0 * 64,
-                                                             (kBwdWaves - idle0) * 64);
-                          });
+                          true, a.slab_color, a.np_color, B, 32u, ActReLU{}, map_of(w), pre_of(), half_of(w),
+                          idle_of());
     // the colour pass's geo grads (global stores of every wave) are complete
     // (the fold's first barrier) and its fold images read before the sigma
     // pass loads g_h and reuses LDS: an LDS-only barrier, so the colour slab
     // row's stores need not land first
     lds_barrier();
-    bwd_phase<64, 1, NHS, false>(sfr, reinterpret_cast<ngp_half*>(lds), reinterpret_cast<float*>(lds), a.g_h, a.enc,
+    bwd_phase<64, 1, NHS, false, false>(sfr, reinterpret_cast<ngp_half*>(lds), reinterpret_cast<float*>(lds), a.g_h, a.enc,
                           InPairMajor{a.B, a.rows}, GiPairMajor{a.g_enc, a.B, a.rows}, true, a.slab_sigma, a.np_sigma,
                           B, 32u, ActReLU{}, map_of(kBwdWaves - 1 - w), []() {}, half_of(kBwdWaves - 1 - w));
     }
@@ -1577,14 +1687,14 @@ int launch_bwd(const void* grad, const void* in, const void* w, const void* imag
                                       gw_dtype, defer, ws, count, st);
 }
 
-template <int NHS, int NHC>
+template <int NHS, int NHC, bool DW>
 int launch_nerf_bwd(const NerfBwdArgs& a, hipStream_t st) {
     // all four depth pairs nerf_backward_impl dispatches fit (134 KB at most)
     static_assert(NerfBwdLds<NHS, NHC>::fits, "nerf backward LDS budget exceeded");
     const uint32_t blocks = bwd_blocks(a.B);
     if (blocks == 0) return NGP_OK;
     constexpr size_t lds_bytes = NerfBwdLds<NHS, NHC>::total;
-    hipLaunchKernelGGL((k_nerf_bwd<NHS, NHC>), dim3(blocks), dim3(kBwdThreads), lds_bytes, st, a);
+    hipLaunchKernelGGL((k_nerf_bwd<NHS, NHC, DW>), dim3(blocks), dim3(kBwdThreads), lds_bytes, st, a);
     return ngp_check_launch("nerf_backward");
 }
 
@@ -1695,7 +1805,7 @@ static int nerf_backward_impl(const void* g_color_out, const void* color_in, con
                               const int32_t* count, const int32_t* rows, uint32_t hidden_dim, uint32_t num_layers,
                               uint32_t hidden_dim_color, uint32_t num_layers_color, void* sigma_workspace,
                               size_t sigma_workspace_bytes, void* color_workspace, size_t color_workspace_bytes,
-                              uint32_t* timing, void* stream) {
+                              uint32_t* timing, void* stream, void* dw_stash = nullptr, uint32_t dw_rows_max = 0) {
     NGP_REQUIRE(!rows || count, NGP_ERR_ARG, "nerf_backward_live: a row list needs its count");
     NGP_REQUIRE(hidden_dim == 64 && hidden_dim_color == 64, NGP_ERR_UNSUPPORTED,
                 "nerf_backward: 64-wide networks only on this build, got %u / %u", hidden_dim, hidden_dim_color);
@@ -1727,14 +1837,82 @@ static int nerf_backward_impl(const void* g_color_out, const void* color_in, con
     a.count = count;
     a.timing = timing;
     a.rows = rows;
+    a.stash = static_cast<ngp_half*>(dw_stash);
+    a.dw_rows_max = dw_stash ? dw_rows_max : 0u;
     hipStream_t st = ngp_stream(stream);
     const uint32_t key = (num_layers - 1) * 8 + (num_layers_color - 1);
-    switch (key) {
-        case 1 * 8 + 1: return launch_nerf_bwd<1, 1>(a, st);
-        case 1 * 8 + 2: return launch_nerf_bwd<1, 2>(a, st);
-        case 2 * 8 + 1: return launch_nerf_bwd<2, 1>(a, st);
-        default: return launch_nerf_bwd<2, 2>(a, st);
+    if (dw_stash) {  // the kernel that holds both regimes
+        switch (key) {
+            case 1 * 8 + 1: return launch_nerf_bwd<1, 1, true>(a, st);
+            case 1 * 8 + 2: return launch_nerf_bwd<1, 2, true>(a, st);
+            case 2 * 8 + 1: return launch_nerf_bwd<2, 1, true>(a, st);
+            default: return launch_nerf_bwd<2, 2, true>(a, st);
+        }
     }
+    switch (key) {
+        case 1 * 8 + 1: return launch_nerf_bwd<1, 1, false>(a, st);
+        case 1 * 8 + 2: return launch_nerf_bwd<1, 2, false>(a, st);
+        case 2 * 8 + 1: return launch_nerf_bwd<2, 1, false>(a, st);
+        default: return launch_nerf_bwd<2, 2, false>(a, st);
+    }
+}
+
+// the light regime's switch as both launches apply it: at most dw_rows_max
+// rows, no more than the stash's whole chunks hold, and at most one chunk per
+// workgroup of the backward over B allocated rows (the product's summation
+// order is the slab path's for that dealing, ngp_reduce.h)
+static uint32_t dw_rows_limit(uint32_t dw_stash_rows, uint32_t dw_rows_max, uint32_t B) {
+    return std::min(std::min(dw_rows_max, dw_stash_rows / ngp_reduce::kBwdChunkRows * ngp_reduce::kBwdChunkRows),
+                    bwd_blocks(B) * ngp_reduce::kBwdChunkRows);
+}
+
+extern "C" size_t ngp_nerf_dw_stash_bytes(uint32_t rows, uint32_t num_layers, uint32_t num_layers_color) {
+    if (num_layers < 2 || num_layers > 3 || num_layers_color < 2 || num_layers_color > 3) return 0;
+    const size_t rec = (size_t)(ngp_reduce::dw_net_units(num_layers_color - 1) + ngp_reduce::dw_net_units(num_layers - 1)) *
+                       ngp_reduce::kBwdChunkRows * sizeof(ngp_half);
+    return (size_t)ngp_div_up(rows, ngp_reduce::kBwdChunkRows) * rec;
+}
+
+extern "C" int ngp_nerf_backward_live_dw(const void* g_color_out, const void* color_in, const void* color_image,
+                                         void* g_h, const void* enc, const void* sigma_image, void* g_enc,
+                                         uint32_t B, const int32_t* live_rows, const int32_t* live_count,
+                                         uint32_t hidden_dim, uint32_t num_layers, uint32_t hidden_dim_color,
+                                         uint32_t num_layers_color, void* sigma_workspace,
+                                         size_t sigma_workspace_bytes, void* color_workspace,
+                                         size_t color_workspace_bytes, uint32_t* timing, void* dw_stash,
+                                         uint32_t dw_stash_rows, uint32_t dw_rows_max, void* stream) {
+    NGP_REQUIRE(live_rows && live_count, NGP_ERR_ARG, "nerf_backward_live_dw: null row list or count");
+    NGP_REQUIRE(dw_stash, NGP_ERR_ARG, "nerf_backward_live_dw: null stash");
+    return nerf_backward_impl(g_color_out, color_in, color_image, g_h, enc, sigma_image, g_enc, B, live_count,
+                              live_rows, hidden_dim, num_layers, hidden_dim_color, num_layers_color, sigma_workspace,
+                              sigma_workspace_bytes, color_workspace, color_workspace_bytes, timing, stream, dw_stash,
+                              dw_rows_limit(dw_stash_rows, dw_rows_max, B));
+}
+
+// The product job of the two networks of ngp_nerf_backward_live_dw (network 0
+// the sigma network, 1 the colour network, as the reduce's arguments list them).
+int ngp_reduce::build_dw_product(const uint32_t* Bs, const uint32_t* in_dims, const uint32_t* hidden_dims,
+                                 const uint32_t* num_layers, void* const* grad_weights, int32_t* nonfinite,
+                                 const int32_t* live_count, const void* dw_stash, uint32_t dw_stash_rows,
+                                 uint32_t dw_rows_max, DwProduct& dj) {
+    dj = DwProduct{};
+    NGP_REQUIRE(dw_stash && live_count, NGP_ERR_ARG, "dw product: null stash or live count");
+    NGP_REQUIRE(Bs[0] == Bs[1] && in_dims[0] == 32 && in_dims[1] == 32 && hidden_dims[0] == 64 &&
+                    hidden_dims[1] == 64 && num_layers[0] >= 2 && num_layers[0] <= 3 && num_layers[1] >= 2 &&
+                    num_layers[1] <= 3,
+                NGP_ERR_UNSUPPORTED, "dw product: the sigma and colour networks of ngp_nerf_backward (64 wide, 32 in)");
+    dj.stash = dw_stash;
+    dj.out[0] = grad_weights[1];
+    dj.out[1] = grad_weights[0];
+    dj.nh[0] = num_layers[1] - 1;
+    dj.nh[1] = num_layers[0] - 1;
+    dj.B = Bs[0];
+    dj.rows_max = dw_rows_limit(dw_stash_rows, dw_rows_max, Bs[0]);
+    dj.wgs = bwd_blocks(Bs[0]);
+    dj.blocks = dw_net_tiles(dj.nh[0]) + dw_net_tiles(dj.nh[1]);
+    dj.live = live_count;
+    dj.nonfinite = nonfinite;
+    return NGP_OK;
 }
 
 extern "C" int ngp_nerf_backward(const void* g_color_out, const void* color_in, const void* color_image,
@@ -1922,6 +2100,44 @@ extern "C" int ngp_ffmlp_reduce(int32_t n, void* const* workspaces, const uint32
     else
         hipLaunchKernelGGL(k_slab_reduce<float>, dim3(blocks), dim3(64 * kReducePhases), 0, ngp_stream(stream), rj);
     return ngp_check_launch("ffmlp_reduce");
+}
+
+// ngp_ffmlp_reduce for the slabs and the stash of ngp_nerf_backward_live_dw, as
+// its own launch (the fused step carries the same blocks in the bin launch):
+// the product workgroups in the light regime, the slab reduce's otherwise.
+namespace {
+__global__ void __launch_bounds__(64 * ngp_reduce::kDwWaves)
+k_nerf_dw_reduce(ReduceJobs jobs, ngp_reduce::DwProduct dj, uint32_t nred) {
+    __shared__ __attribute__((aligned(16))) float part[ngp_reduce::kReducePhases * 256];
+    const bool light = ngp_reduce::dw_light(dj);
+    if (blockIdx.x < nred) {
+        if (!light)
+            ngp_reduce::slab_reduce_block<ngp_half, 64 * ngp_reduce::kDwWaves>(jobs, blockIdx.x,
+                                                                              reinterpret_cast<float(*)[64]>(part));
+    } else if (light) {
+        ngp_reduce::dw_product_block(dj, blockIdx.x - nred, part);
+    }
+}
+}  // namespace
+
+extern "C" int ngp_nerf_dw_reduce(void* const* workspaces, const uint32_t* Bs, const uint32_t* in_dims,
+                                  const uint32_t* hidden_dims, const uint32_t* num_layers,
+                                  void* const* grad_weights, int32_t* nonfinite, const int32_t* live_count,
+                                  const void* dw_stash, uint32_t dw_stash_rows, uint32_t dw_rows_max, void* stream) {
+    NGP_REQUIRE(workspaces && Bs && in_dims && hidden_dims && num_layers && grad_weights, NGP_ERR_ARG,
+                "nerf_dw_reduce: null argument");
+    ngp_reduce::DwProduct dj{};
+    if (int e = ngp_reduce::build_dw_product(Bs, in_dims, hidden_dims, num_layers, grad_weights, nonfinite,
+                                             live_count, dw_stash, dw_stash_rows, dw_rows_max, dj))
+        return e;
+    ReduceJobs rj{};
+    const uint32_t nred = ngp_reduce::build_reduce_jobs(2, workspaces, Bs, in_dims, hidden_dims, num_layers,
+                                                        grad_weights, nonfinite, rj);
+    rj.live = live_count;
+    if (nred == 0) return NGP_OK;
+    hipLaunchKernelGGL(k_nerf_dw_reduce, dim3(nred + dj.blocks), dim3(64 * ngp_reduce::kDwWaves), 0,
+                       ngp_stream(stream), rj, dj, nred);
+    return ngp_check_launch("nerf_dw_reduce");
 }
 
 extern "C" int ngp_ffmlp_allocate_splitk(size_t size) { (void)size; return NGP_OK; }

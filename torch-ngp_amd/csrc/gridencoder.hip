@@ -898,7 +898,8 @@ NGP_DEV void bin_block(const ngp_half* __restrict__ grad, const float* __restric
                        int32_t grad_layout, int32_t* __restrict__ nonfinite, const ngp_reduce::ReduceJobs& rj,
                        uint32_t nred, uint32_t* __restrict__ timing, const BinLego& next_batch,
                        unsigned long long* __restrict__ spill, uint32_t* __restrict__ spill_bad,
-                       uint32_t* __restrict__ rows_out, uint32_t bx, uint32_t by, uint32_t gy, uint32_t* lds) {
+                       uint32_t* __restrict__ rows_out, uint32_t bx, uint32_t by, uint32_t gy, uint32_t* lds,
+                       const ngp_reduce::DwProduct& dw) {
     constexpr uint32_t NC = 1u << D, NW = kBinPts / 64;
     constexpr uint32_t BPT = (NBMAX + kBinPts - 1) / kBinPts;  // bins per thread in the reservation step
     uint32_t* cnt = lds;                 // [NBMAX]
@@ -931,11 +932,21 @@ NGP_DEV void bin_block(const ngp_half* __restrict__ grad, const float* __restric
     if (bx >= bp.nlev) {
         // (stamps build: each extra block's start / end on the constant clock,
         // role 0 the dW reduce, role 1 the sampler)
+        // When the launch carries a dW product job (ngp_reduce.h), the reduce
+        // column is the product column in the light regime of
+        // ngp_nerf_backward_live_dw: its first dw.blocks workgroups (one per
+        // dW tile, never more than the reduce's blocks) form the weight
+        // gradients from the stash and the others return at once; in the
+        // other regime the column is the slab reduce as ever, so that launch
+        // has the same workgroups as one without the job.
         [[maybe_unused]] const uint32_t xrole = nred && bx == bp.nlev ? 0u : 1u;
         XSTAMP(xrole, by, 0);
         if (nred && bx == bp.nlev) {
-            if (by < nred)
+            if (ngp_reduce::dw_light(dw)) {
+                if (by < dw.blocks) ngp_reduce::dw_product_block(dw, by, reinterpret_cast<float*>(stage));
+            } else if (by < nred) {
                 ngp_reduce::slab_reduce_block<ngp_half, kBinPts>(rj, by, reinterpret_cast<float(*)[64]>(stage));
+            }
         } else if (by < next_batch.nlego) {
             const BinLego& q = next_batch;
             ngp_head::lego_rays_block(by, q.nlego, q.poses, q.sc, q.N, q.st, q.out);
@@ -1211,11 +1222,12 @@ k_grid_bwd_bin(const ngp_half* __restrict__ grad, const float* __restrict__ inpu
                InMap im, BinPlan bp, uint32_t* __restrict__ cursor, BinItem* __restrict__ items,
                int32_t grad_layout, int32_t* __restrict__ nonfinite, ngp_reduce::ReduceJobs rj, uint32_t nred,
                uint32_t* __restrict__ timing, BinLego next_batch, unsigned long long* __restrict__ spill,
-               uint32_t* __restrict__ spill_bad, uint32_t* __restrict__ rows_out) {
+               uint32_t* __restrict__ spill_bad, uint32_t* __restrict__ rows_out, ngp_reduce::DwProduct dw) {
+    static_assert(kBinPts == 64 * ngp_reduce::kDwWaves, "a dW product workgroup is a bin workgroup");
     extern __shared__ __attribute__((aligned(16))) uint32_t bin_lds[];  // bin_lds_words<NBMAX>()
     bin_block<D, NBMAX, false>(grad, inputs, offsets, grad_grid, B, L, lv, gridtype, align_corners, interp, im, bp,
                                cursor, items, grad_layout, nonfinite, rj, nred, timing, next_batch, spill, spill_bad,
-                               rows_out, blockIdx.x, blockIdx.y, gridDim.y, bin_lds);
+                               rows_out, blockIdx.x, blockIdx.y, gridDim.y, bin_lds, dw);
 }
 
 // Persistent accumulation: every workgroup reads all bins' counts, forms the
@@ -2088,7 +2100,8 @@ k_grid_bwd_fused(const ngp_half* __restrict__ grad, const float* __restrict__ in
         }
         bin_block<D, NBMAX, true>(grad, inputs, offsets, grad_grid, B, L, lv, gridtype, align_corners, interp, im,
                                   bp, cursor, items, grad_layout, nonfinite, rj, nred, timing, next_batch, spill,
-                                  spill_bad, nullptr, bx, by, ycap, reinterpret_cast<uint32_t*>(acc));
+                                  spill_bad, nullptr, bx, by, ycap, reinterpret_cast<uint32_t*>(acc),
+                                  ngp_reduce::DwProduct{});
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores and atomics have landed
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -2608,7 +2621,8 @@ int bwd_fused_impl(const void* grad, const float* xyz, float bound, const int32_
                    uint32_t gridtype, int32_t align_corners, uint32_t interp, const int32_t* offsets_host,
                    void* workspace, size_t workspace_bytes, int32_t grad_layout, int32_t* nonfinite,
                    void* stream, const ngp_reduce::ReduceJobs* rj = nullptr,
-                   uint32_t nred = 0, const BinLego* blp = nullptr, const int32_t* rows = nullptr) {
+                   uint32_t nred = 0, const BinLego* blp = nullptr, const int32_t* rows = nullptr,
+                   const ngp_reduce::DwProduct* dwp = nullptr) {
     if (int e = check_common(L, grad, offsets, grad_embeddings)) return e;
     const bool zeroed = (grad_layout & NGP_GRID_GRAD_ZEROED) != 0;
     const bool external = (grad_layout & NGP_GRID_CURSORS_EXTERNAL) != 0;
@@ -2650,6 +2664,10 @@ int bwd_fused_impl(const void* grad, const float* xyz, float bound, const int32_
         if (!rj) nred = 0;
         // + one column of the next batch's sampler blocks (blp, fully binned plans only)
         const BinLego bl = blp && bp.nlev == L ? *blp : BinLego{};
+        // the dW product job rides in the reduce column (its tiles: fewer than the reduce's blocks)
+        const ngp_reduce::DwProduct dw = dwp && nred ? *dwp : ngp_reduce::DwProduct{};
+        NGP_REQUIRE(dw.blocks <= nred, NGP_ERR_ARG, "grid_encode_backward_fused: %u dW tiles for %u reduce blocks",
+                    dw.blocks, nred);
         const dim3 grid(bp.nlev + (nred ? 1u : 0u) + (bl.nlego ? 1u : 0u),
                         std::max(std::max(std::min(ngp_div_up(B, kBinPts), kBinYCap), nred), bl.nlego));
         uint32_t nbmax = 0;
@@ -2660,7 +2678,7 @@ int bwd_fused_impl(const void* grad, const float* xyz, float bound, const int32_
         const bool fused_fits = kFusedBwd != 2 ||
                                 bp.nlev * std::min(ngp_div_up(B, kBinPts), 8u) + nred + bl.nlego + kAccImageWgs + 64 <=
                                     2 * ngp_num_cus();
-        if (kFusedBwd && waves_cfg && fused_fits && B >= 1) {
+        if (kFusedBwd && waves_cfg && fused_fits && B >= 1 && !dw.blocks) {
             const uint32_t img_bins = bp.img_bins;
             auto two_fit = [](size_t d) { return 2 * (d + kAccStaticLds) <= 160 * 1024; };
             const size_t dyn_all = (2 * (size_t)bp.total_bins + 1) * sizeof(uint32_t);
@@ -2698,11 +2716,13 @@ int bwd_fused_impl(const void* grad, const float* xyz, float bound, const int32_
             if (nbmax <= kMaxBinsPerLevel)
                 k_grid_bwd_bin<3, kMaxBinsPerLevel><<<grid, kBinPts, bin_lds_words<kMaxBinsPerLevel>() * 4, st>>>(
                     (const ngp_half*)grad, xyz, offsets, (ngp_half*)grad_embeddings, B, L, lv, gridtype, ac, interp,
-                    im, bp, cursor, items, grad_layout, nonfinite, rjv, nred, timing, bl, spill, spill_bad, retire + kRowsWord);
+                    im, bp, cursor, items, grad_layout, nonfinite, rjv, nred, timing, bl, spill, spill_bad, retire + kRowsWord,
+                    dw);
             else
                 k_grid_bwd_bin<3, kMaxBinsPerLevelBig><<<grid, kBinPts, bin_lds_words<kMaxBinsPerLevelBig>() * 4, st>>>(
                     (const ngp_half*)grad, xyz, offsets, (ngp_half*)grad_embeddings, B, L, lv, gridtype, ac, interp,
-                    im, bp, cursor, items, grad_layout, nonfinite, rjv, nred, timing, bl, spill, spill_bad, retire + kRowsWord);
+                    im, bp, cursor, items, grad_layout, nonfinite, rjv, nred, timing, bl, spill, spill_bad, retire + kRowsWord,
+                    dw);
             // the hashed levels' bins one per wave (wave_bin) when the grad is
             // cleared and the caller clears the cursors (the fused step): the
             // image path then covers only the dense levels' bins, on the first
@@ -2835,7 +2855,8 @@ static int reduce_batch_impl(
     int32_t grad_layout, int32_t* nonfinite, int32_t n_nets, void* const* mlp_workspaces, const uint32_t* mlp_Bs,
     const uint32_t* in_dims, const uint32_t* hidden_dims, const uint32_t* num_layers, void* const* grad_weights,
     int32_t* mlp_nonfinite, const ngp_batch_job* job, void* stream, const int32_t* rows,
-    const ngp_image_source* src = nullptr) {
+    const ngp_image_source* src = nullptr, const void* dw_stash = nullptr, uint32_t dw_stash_rows = 0,
+    uint32_t dw_rows_max = 0) {
     NGP_REQUIRE(job && job->state && job->counter && job->poses && job->N > 0 && job->n_poses > 0, NGP_ERR_ARG,
                 "grid_encode_backward_fused_reduce_batch: incomplete batch job");
     NGP_REQUIRE(job->nboxes >= 0 && job->nboxes <= ngp_head::kMaxBoxes, NGP_ERR_ARG,
@@ -2858,6 +2879,15 @@ static int reduce_batch_impl(
     const uint32_t nred = ngp_reduce::build_reduce_jobs(n_nets, mlp_workspaces, mlp_Bs, in_dims, hidden_dims,
                                                         num_layers, grad_weights, mlp_nonfinite, rj);
     if (rows) rj.live = count;  // the slabs of ngp_nerf_backward_live over the same live rows
+    // the stash of ngp_nerf_backward_live_dw: the product column (or its own launch where nothing is binned)
+    ngp_reduce::DwProduct dw{};
+    if (dw_stash) {
+        NGP_REQUIRE(rows && n_nets == 2, NGP_ERR_ARG,
+                    "grid_encode_backward_fused_dw_batch: a row list and the sigma and colour networks");
+        if (int e = ngp_reduce::build_dw_product(mlp_Bs, in_dims, hidden_dims, num_layers, grad_weights,
+                                                 mlp_nonfinite, count, dw_stash, dw_stash_rows, dw_rows_max, dw))
+            return e;
+    }
     bool binned = false;
     if (workspace && offsets_host && C == 2 && D == 3 && L >= 1 && L <= kMaxLevels) {
         GridLevels lv;
@@ -2865,14 +2895,18 @@ static int reduce_batch_impl(
         binned = make_bin_plan(offsets_host, L, D, lv, align_corners != 0, B).nlev > 0;
     }
     if (!binned) {  // no bin launch to carry the reduce: it goes first, on its own
-        if (int e = ngp_reduce::launch_slab_reduce(rj, nred, stream)) return e;
+        if (dw_stash) {
+            if (int e = ngp_nerf_dw_reduce(mlp_workspaces, mlp_Bs, in_dims, hidden_dims, num_layers, grad_weights,
+                                           mlp_nonfinite, count, dw_stash, dw_stash_rows, dw_rows_max, stream))
+                return e;
+        } else if (int e = ngp_reduce::launch_slab_reduce(rj, nred, stream)) return e;
         return bwd_fused_impl(grad, xyz, bound, offsets, grad_embeddings, B, count, D, C, L, S, H, gridtype,
                               align_corners, interp, offsets_host, workspace, workspace_bytes, grad_layout,
                               nonfinite, stream, nullptr, 0, &bl, rows);
     }
     return bwd_fused_impl(grad, xyz, bound, offsets, grad_embeddings, B, count, D, C, L, S, H, gridtype,
                           align_corners, interp, offsets_host, workspace, workspace_bytes, grad_layout, nonfinite,
-                          stream, &rj, nred, &bl, rows);
+                          stream, &rj, nred, &bl, rows, dw_stash ? &dw : nullptr);
 }
 
 extern "C" int ngp_grid_encode_backward_fused_reduce_batch(
@@ -2920,6 +2954,30 @@ extern "C" int ngp_grid_encode_backward_fused_reduce_batch_images(
                              align_corners, interp, offsets_host, workspace, workspace_bytes, grad_layout, nonfinite,
                              n_nets, mlp_workspaces, mlp_Bs, in_dims, hidden_dims, num_layers, grad_weights,
                              mlp_nonfinite, job, stream, live_rows, src);
+}
+
+extern "C" int ngp_grid_encode_backward_fused_dw_batch_live(
+    const void* grad, const float* xyz, float bound, const int32_t* offsets, void* grad_embeddings, uint32_t B,
+    const int32_t* live_rows, const int32_t* live_count, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+    uint32_t gridtype, int32_t align_corners, uint32_t interp, const int32_t* offsets_host, void* workspace,
+    size_t workspace_bytes, int32_t grad_layout, int32_t* nonfinite, int32_t n_nets, void* const* mlp_workspaces,
+    const uint32_t* mlp_Bs, const uint32_t* in_dims, const uint32_t* hidden_dims, const uint32_t* num_layers,
+    void* const* grad_weights, int32_t* mlp_nonfinite, const ngp_batch_job* job, const ngp_image_source* src,
+    const void* dw_stash, uint32_t dw_stash_rows, uint32_t dw_rows_max, void* stream) {
+    NGP_REQUIRE(live_rows && live_count && dw_stash, NGP_ERR_ARG,
+                "grid_encode_backward_fused_dw_batch_live: null row list or stash");
+    if (src) {  // the next batch from an image source, as ngp_grid_encode_backward_fused_reduce_batch_images
+        if (int e = ngp_head::check_image_source(src, "grid_encode_backward_fused_dw_batch_live")) return e;
+        if (job)
+            if (int e = ngp_head::check_error_map_draw(src, job->N, "grid_encode_backward_fused_dw_batch_live"))
+                return e;
+        NGP_REQUIRE(!job || (!job->boxes && job->nboxes == 0), NGP_ERR_ARG,
+                    "grid_encode_backward_fused_dw_batch_live: an image job carries no boxes");
+    }
+    return reduce_batch_impl(grad, xyz, bound, offsets, grad_embeddings, B, live_count, D, C, L, S, H, gridtype,
+                             align_corners, interp, offsets_host, workspace, workspace_bytes, grad_layout, nonfinite,
+                             n_nets, mlp_workspaces, mlp_Bs, in_dims, hidden_dims, num_layers, grad_weights,
+                             mlp_nonfinite, job, stream, live_rows, src, dw_stash, dw_stash_rows, dw_rows_max);
 }
 
 #ifdef NGP_STAMPS

@@ -88,6 +88,10 @@ def _vp_array(ptrs):
 #   emit_inline   the march launch emits its samples itself (no emit launch)
 #   draw_ahead    the next batch is drawn in the grid backward's bin launch
 #   live_rows     the backwards walk the rows with a nonzero gradient only
+#   dw_rows       with live_rows, world 1 and no background model: steps of at most
+#                 this many live rows form the MLP weight gradients in the bin
+#                 launch, from operands the backward stashes, instead of in the
+#                 backward itself: the same bits (0: always in the backward)
 #   dp_graph      data parallel over RCCL: the whole step is one graph
 #   density_sort  partial density updates draw their cells as order statistics, in
 #                 Morton order (False: the counter-RNG draws in draw order)
@@ -102,7 +106,7 @@ def _vp_array(ptrs):
 DEFAULT_OPTIONS = dict(table16=False, split_head=False, split_reduce=False, split_fwd=False, split_bwd=False,
                        march_adam=True, tail_in_fwd=True, emit_inline=True, draw_ahead=True, live_rows=True,
                        dp_graph=True, density_sort=True, sparse_exchange=False, exact_reduce=False,
-                       density_run_max=False)
+                       density_run_max=False, dw_rows=8192)
 
 
 def perm_mult(n):
@@ -151,7 +155,7 @@ class FusedTrainer:
         for k, v in (options or {}).items():
             if k not in opts:
                 raise ValueError(f"FusedTrainer: unknown option {k!r} (known: {sorted(opts)})")
-            opts[k] = bool(v)
+            opts[k] = max(0, int(v)) if k == "dw_rows" else bool(v)  # (dw_rows: a row count)
         self.options = opts
         assert model.cuda_ray, "the fused step marches the density bitfield (cuda_ray=True)"
         enc = model.encoder
@@ -518,6 +522,15 @@ class FusedTrainer:
             i32 = torch.int32
             self._live_bufs = dict(ray_rows=z(M, dtype=i32), cnt=z(N, dtype=i32), rows=z(M, dtype=i32),
                                    total=z(4, dtype=i32))
+        # ... and, up to dw_rows live rows, leave the weight gradients to the bin
+        # launch (ngp_nerf_backward_live_dw): the stash is scratch, not checkpointed
+        self._dw_rows = int(opts["dw_rows"]) if self._live and not self.dp and not self._bg else 0
+        if self._dw_rows:
+            # (the kernels cap the switch at one 32-row chunk per backward workgroup, at most 256 of them)
+            wgs = min(256, -(-(-(-M // 32)) // 4))
+            self._dw_cap = min(M, (self._dw_rows + 31) // 32 * 32, 32 * wgs)
+            self._dw_stash = z(int(nat.lib().ngp_nerf_dw_stash_bytes(self._dw_cap, self.sig_net.num_layers,
+                                                                     self.col_net.num_layers)), dtype=torch.uint8)
         if self._loss_job is not None and self._live:
             # (a batch's composite runs its live form exactly when it draws ahead: see _network)
             lb, lj = self._live_bufs, self._loss_job
@@ -1130,7 +1143,15 @@ class FusedTrainer:
             self._background_backward()
         if self._one_bwd:  # both networks' backward in one launch (ngp_nerf_backward)
             timing = P(self.grid_ws) + self._grid_timing_at if self._grid_timing_at else None
-            if live:
+            if live and self._dw_rows:
+                chk(lib.ngp_nerf_backward_live_dw(P(self.g_color_out), P(self.color_in), P(img[1]), P(self.g_h),
+                                                  P(self.enc_out), P(img[0]), P(self.g_enc), M, P(lv["rows"]),
+                                                  P(lv["total"]), sn.hidden_dim, sn.num_layers, cn.hidden_dim,
+                                                  cn.num_layers, P(self.mlp_ws[0]), self.mlp_ws[0].numel(),
+                                                  P(self.mlp_ws[1]), self.mlp_ws[1].numel(), timing,
+                                                  P(self._dw_stash), self._dw_cap, self._dw_rows, s),
+                    "nerf_backward_live_dw")
+            elif live:
                 chk(lib.ngp_nerf_backward_live(P(self.g_color_out), P(self.color_in), P(img[1]), P(self.g_h),
                                                P(self.enc_out), P(img[0]), P(self.g_enc), M, P(lv["rows"]),
                                                P(lv["total"]), sn.hidden_dim, sn.num_layers, cn.hidden_dim,
@@ -1212,10 +1233,16 @@ class FusedTrainer:
             iargs = (P(self.g_enc), P(self.xyzs), float(m.bound), P(e.offsets), P(self.grads[0]), M, rows, n,
                      *grid_args[:-1], self._offsets_host, P(self.grid_ws), self.grid_ws.numel(), self._grid_flags,
                      self._inf_flag)
-            chk(lib.ngp_grid_encode_backward_fused_reduce_batch_images(
-                *iargs, 2, pk["ws"], pk["B"], pk["ins"], pk["hid"], pk["nl"], pk["gw"], self._inf_flag,
-                ctypes.byref(self._batch_job), ctypes.byref(self._src), s),
-                "grid_backward_fused_reduce_batch_images")
+            if self._dw_rows:
+                chk(lib.ngp_grid_encode_backward_fused_dw_batch_live(
+                    *iargs, 2, pk["ws"], pk["B"], pk["ins"], pk["hid"], pk["nl"], pk["gw"], self._inf_flag,
+                    ctypes.byref(self._batch_job), ctypes.byref(self._src), P(self._dw_stash), self._dw_cap,
+                    self._dw_rows, s), "grid_backward_fused_dw_batch_live")
+            else:
+                chk(lib.ngp_grid_encode_backward_fused_reduce_batch_images(
+                    *iargs, 2, pk["ws"], pk["B"], pk["ins"], pk["hid"], pk["nl"], pk["gw"], self._inf_flag,
+                    ctypes.byref(self._batch_job), ctypes.byref(self._src), s),
+                    "grid_backward_fused_reduce_batch_images")
             self._ahead = True
         elif draw and self._live:
             # over the live rows (the MLP backward wrote g_enc for those only)
@@ -1223,10 +1250,17 @@ class FusedTrainer:
             largs = (P(self.g_enc), P(self.xyzs), float(m.bound), P(e.offsets), P(self.grads[0]), M, P(lv["rows"]),
                      P(lv["total"]), *grid_args[:-1], self._offsets_host, P(self.grid_ws), self.grid_ws.numel(),
                      self._grid_flags, self._inf_flag)
-            chk(lib.ngp_grid_encode_backward_fused_reduce_batch_live(*largs, 2, pk["ws"], pk["B"], pk["ins"],
-                                                                     pk["hid"], pk["nl"], pk["gw"], self._inf_flag,
-                                                                     ctypes.byref(self._batch_job), s),
-                "grid_backward_fused_reduce_batch_live")
+            if self._dw_rows:
+                chk(lib.ngp_grid_encode_backward_fused_dw_batch_live(
+                    *largs, 2, pk["ws"], pk["B"], pk["ins"], pk["hid"], pk["nl"], pk["gw"], self._inf_flag,
+                    ctypes.byref(self._batch_job), None, P(self._dw_stash), self._dw_cap, self._dw_rows, s),
+                    "grid_backward_fused_dw_batch_live")
+            else:
+                chk(lib.ngp_grid_encode_backward_fused_reduce_batch_live(*largs, 2, pk["ws"], pk["B"], pk["ins"],
+                                                                         pk["hid"], pk["nl"], pk["gw"],
+                                                                         self._inf_flag,
+                                                                         ctypes.byref(self._batch_job), s),
+                    "grid_backward_fused_reduce_batch_live")
             self._ahead = True
         elif draw:
             # + the next step's batch, as another column of the bin launch
