@@ -680,6 +680,27 @@ int ngp_nerf_backward_live_dw(const void* g_color_out, const void* color_in, con
                               void* sigma_workspace, size_t sigma_workspace_bytes, void* color_workspace,
                               size_t color_workspace_bytes, uint32_t* timing, void* dw_stash,
                               uint32_t dw_stash_rows, uint32_t dw_rows_max, void* stream);
+/* ngp_nerf_backward_live_dw with the list's join in the same launch: the
+ * arguments are the per-ray lists ngp_nerf_composite_loss_lists leaves (rays
+ * [N,3], live_cnt [N] 16-byte aligned, ray_rows [B]) instead of a finished
+ * list. Every workgroup sums the counts, finds the list positions of its own
+ * chunks and keeps their rows in LDS; it also stores them to live_rows, and
+ * workgroup 0 stores live_total, so live_rows[0, *live_total), *live_total and
+ * every output are those of ngp_nerf_composite_loss_live +
+ * ngp_nerf_backward_live_dw bit for bit (entries of live_rows past the total
+ * are not written). No workgroup waits for another. One pass holds
+ * ngp_nerf_backward_join_max_rays() rays (4096) and B <= 262144 rows (32
+ * chunks per workgroup): beyond either the call returns NGP_ERR_ARG and
+ * launches nothing. tests/test_gpu_live_join.py. */
+int ngp_nerf_backward_join_dw(const void* g_color_out, const void* color_in, const void* color_image, void* g_h,
+                              const void* enc, const void* sigma_image, void* g_enc, uint32_t B,
+                              const int32_t* rays, uint32_t N, const int32_t* live_cnt, const int32_t* ray_rows,
+                              int32_t* live_rows, int32_t* live_total, uint32_t hidden_dim, uint32_t num_layers,
+                              uint32_t hidden_dim_color, uint32_t num_layers_color, void* sigma_workspace,
+                              size_t sigma_workspace_bytes, void* color_workspace, size_t color_workspace_bytes,
+                              uint32_t* timing, void* dw_stash, uint32_t dw_stash_rows, uint32_t dw_rows_max,
+                              void* stream);
+uint32_t ngp_nerf_backward_join_max_rays(void);
 /* The weight gradients (fp16) of ngp_nerf_backward_live_dw in one launch:
  * network 0 the sigma network, 1 the colour network (workspaces, Bs = the
  * backward's B twice, shapes and grad_weights as ngp_ffmlp_reduce lists them).
@@ -751,6 +772,17 @@ int ngp_nerf_composite_loss_live(const float* sigma, const void* color_out, cons
                                  void* state, void* grad_color_out, void* grad_h_sigma, float* out_image,
                                  float* out_ws, float* loss_ray, int32_t* ray_rows, int32_t* live_cnt,
                                  int32_t* live_rows, int32_t* live_total, void* stream);
+/* ngp_nerf_composite_loss_live's first launch alone: the per-ray lists
+ * ray_rows [M] (ray n's live rows, in order, from its first row rays[3 n + 1])
+ * and live_cnt [N] (their count; 0 for a ray dropped for overflowing M; 16-byte
+ * aligned), for a backward that joins the list itself
+ * (ngp_nerf_backward_join_dw). One launch. */
+int ngp_nerf_composite_loss_lists(const float* sigma, const void* color_out, const void* h_sigma,
+                                  const float* deltas, const int32_t* rays, uint32_t M, uint32_t N, float T_thresh,
+                                  float density_scale, const float* gt, uint32_t gt_channels, const float* bg,
+                                  void* state, void* grad_color_out, void* grad_h_sigma, float* out_image,
+                                  float* out_ws, float* loss_ray, int32_t* ray_rows, int32_t* live_cnt,
+                                  void* stream);
 /* The depth-supervised loss (the reference's train_step, nerf/utils.py:545-553
  * and :951-954): per ray, with pred the composite's own depth (0 for a ray
  * without samples or dropped for overflowing M),
@@ -783,6 +815,14 @@ int ngp_nerf_composite_loss_depth(const float* sigma, const void* color_out, con
                                   float density_scale, const float* gt, uint32_t gt_channels, const float* bg,
                                   void* state, void* grad_color_out, void* grad_h_sigma, float* out_image,
                                   float* out_ws, float* loss_ray, const ngp_depth_loss_job* job, void* stream);
+/* .._depth as ngp_nerf_composite_loss_lists: the job's ray_rows and live_cnt are
+ * required and written, its live_rows and live_total are not used. One launch. */
+int ngp_nerf_composite_loss_depth_lists(const float* sigma, const void* color_out, const void* h_sigma,
+                                        const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                        float T_thresh, float density_scale, const float* gt, uint32_t gt_channels,
+                                        const float* bg, void* state, void* grad_color_out, void* grad_h_sigma,
+                                        float* out_image, float* out_ws, float* loss_ray,
+                                        const ngp_depth_loss_job* job, void* stream);
 /* scaler_enabled of the optimizer entries: GradScaler off; on, with its inf
  * check as a sweep over the grads; on, with the check already made by the
  * kernels that wrote the grads into the state's flag (ngp_fused_inf_flag). */

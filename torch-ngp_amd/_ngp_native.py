@@ -158,6 +158,14 @@ SIGNATURES = {
                                      c_vp],
     "ngp_nerf_composite_loss_depth": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
                                       c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_nerf_composite_loss_lists": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
+                                      c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_nerf_composite_loss_depth_lists": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
+                                            c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_nerf_backward_join_dw": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp,
+                                  c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_u32,
+                                  c_u32, c_vp],
+    "ngp_nerf_backward_join_max_rays": [],
     "ngp_fused_optimizer_step": [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_f32, c_f32,
                                  c_i32, c_i32, c_f32, c_f32, c_f32, c_i32, c_i32, c_u32, c_vp, c_vp,
                                  c_vp, c_vp, c_vp],
@@ -212,6 +220,7 @@ _RESTYPES = {
     "ngp_grid_encode_backward_fused_workspace_bytes": c_sz,
     "ngp_ffmlp_image_bytes": c_sz,
     "ngp_nerf_dw_stash_bytes": c_sz,
+    "ngp_nerf_backward_join_max_rays": c_u32,
     "ngp_density_grid_draw_workspace_bytes": c_sz,
     "ngp_density_grid_sort_workspace_bytes": c_sz,
     "ngp_density_grid_ostat_workspace_bytes": c_sz,

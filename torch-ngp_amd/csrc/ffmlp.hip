@@ -24,6 +24,7 @@
 //     order: no atomics, bit-reproducible weight gradients.
 #include "ffmlp_pack.h"
 #include "ngp_common.h"
+#include "ngp_dpp.h"
 #include "ngp_reduce.h"
 #include "sh_basis.h"
 
@@ -93,6 +94,28 @@ NGP_DEV void copy_frags(half8* __restrict__ lds, const half8* __restrict__ image
     }
 }
 
+// copy_frags in two halves, for work between the requests and the LDS stores
+// (the NeRF backward's join): v holds the thread's fragments meanwhile.
+template <int FRAGS, int THREADS, int PER>
+NGP_DEV void load_frags(const half8* __restrict__ image, half8 (&v)[PER]) {
+    constexpr int TOTAL = FRAGS * 64;
+    static_assert(PER == (TOTAL + THREADS - 1) / THREADS, "one register per round");
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int t = k * THREADS + (int)threadIdx.x;
+        v[k] = image[(k + 1) * THREADS <= TOTAL ? t : min(t, TOTAL - 1)];
+    }
+}
+template <int FRAGS, int THREADS, int PER>
+NGP_DEV void store_frags(half8* __restrict__ lds, const half8 (&v)[PER]) {
+    constexpr int TOTAL = FRAGS * 64;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int t = k * THREADS + (int)threadIdx.x;
+        if ((k + 1) * THREADS <= TOTAL || t < TOTAL) lds[t] = v[k];
+    }
+}
+
 // An image copied by `nthr` threads of the workgroup (tid in [0, nthr)), four
 // loads of a thread in flight per round: the NeRF backward's idle waves copy
 // the sigma image during the colour pass.
@@ -145,6 +168,22 @@ NGP_DEV uint32_t clamp_row(uint32_t row, uint32_t B) { return row < B ? row : (B
 // A row list (the live rows of a step, see ngp_nerf_composite_loss_live): row r of
 // the B rows an MLP call processes is map[r]; null: r itself.
 NGP_DEV uint32_t map_row(const int32_t* map, uint32_t r) { return map ? (uint32_t)map[r] : r; }
+// The row list of a workgroup that joined its own part of it (k_nerf_bwd's
+// join prologue): the entries of its chunks b, b + G, ... lie in LDS, 32 per
+// chunk in dealing order. A position outside them (the loaders' clamped reads,
+// whose values are masked) reads entry 0, which always holds a row.
+struct LdsRows {
+    const int32_t* list;
+    uint32_t b, n;  // the workgroup's first chunk and its number of chunks
+    float g, inv_g;  // the workgroups (chunk stride) and 1 / G
+};
+NGP_DEV uint32_t map_row(const LdsRows& m, uint32_t r) {
+    const uint32_t c = r / (16 * kNB), x = c - m.b;
+    // x = j G exactly for an own chunk (x < 2^24: the quotient estimate is verified)
+    const uint32_t j = (uint32_t)(((float)x + 0.5f) * m.inv_g);
+    const bool own = c >= m.b && j < m.n && (float)j * m.g == (float)x;
+    return (uint32_t)m.list[own ? j * (16 * kNB) + (r & (16 * kNB - 1)) : 0u];
+}
 
 // Activation enum of ffmlp.py:89-96 / utils.h:29-37.
 enum Act : uint32_t { kReLU = 0, kExp = 1, kSine = 2, kSigmoid = 3, kSquareplus = 4, kSoftplus = 5, kNone = 6 };
@@ -307,9 +346,9 @@ NGP_DEV void pack_act(const f32x4 (&acc)[NB][MT], ActReLU, half8 (&out)[NB][KS])
 }
 
 // load a [rows, width] fp16 row-major block as natural-K B operands
-template <int KS, int NB>
+template <int KS, int NB, typename RM = const int32_t*>
 NGP_DEV void load_rows(const ngp_half* __restrict__ src, uint32_t width, uint32_t row0, uint32_t B,
-                       half8 (&out)[NB][KS], const int32_t* map = nullptr) {
+                       half8 (&out)[NB][KS], const RM& map = RM{}) {
     const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -327,8 +366,9 @@ NGP_DEV void load_rows(const ngp_half* __restrict__ src, uint32_t width, uint32_
 }
 
 // First-layer input loaders (natural-K B operands).
-struct InRowMajor {  // [B, width] row-major
-    const int32_t* map = nullptr;  // row list, or null
+template <typename RM>
+struct InRowMajorT {  // [B, width] row-major
+    RM map = RM{};  // row list, or null
     template <int KS, int NB>
     NGP_DEV void operator()(const ngp_half* __restrict__ src, uint32_t width, uint32_t row0, uint32_t B,
                             half8 (&out)[NB][KS]) const {
@@ -339,9 +379,11 @@ struct InRowMajor {  // [B, width] row-major
 // [L, B, C = 2] layout, so the grid kernels read and write whole lines per
 // level. Lane (g, c) gathers its 8 columns as 4 pairs; the 16 lanes of a
 // group read 64 contiguous bytes per pair.
-struct InPairMajor {
+using InRowMajor = InRowMajorT<const int32_t*>;
+template <typename RM>
+struct InPairMajorT {
     uint32_t ld;  // allocated rows
-    const int32_t* map = nullptr;  // row list, or null
+    RM map = RM{};  // row list, or null
     template <int KS, int NB>
     NGP_DEV void operator()(const ngp_half* __restrict__ src, uint32_t width, uint32_t row0, uint32_t B,
                             half8 (&out)[NB][KS]) const {
@@ -366,6 +408,8 @@ struct InPairMajor {
         }
     }
 };
+
+using InPairMajor = InPairMajorT<const int32_t*>;
 
 // The forward kernels' pair-major loads (k_density_fwd, k_nerf_fwd): one
 // buffer descriptor over the [width / 2][ld] pairs, the lane's pair row in the
@@ -996,9 +1040,10 @@ struct GiStore {
     }
 };
 
-struct GiNerfGeo {
+template <typename RM>
+struct GiNerfGeoT {
     ngp_half* gh;
-    const int32_t* map = nullptr;  // row list, or null
+    RM map = RM{};  // row list, or null
     template <int IN_MT, int NB>
     NGP_DEV void operator()(uint32_t row0, uint32_t B, uint32_t, const f32x4 (&t)[NB][IN_MT]) const {
         static_assert(IN_MT == 2, "the color network input is 32 wide");  // see launch_bwd
@@ -1023,11 +1068,14 @@ struct GiNerfGeo {
     }
 };
 
+using GiNerfGeo = GiNerfGeoT<const int32_t*>;
+
 // [in_dim / 2][ld][2] pair-major input gradient (see InPairMajor)
-struct GiPairMajor {
+template <typename RM>
+struct GiPairMajorT {
     ngp_half* gi;
     uint32_t ld;
-    const int32_t* map = nullptr;  // row list, or null
+    RM map = RM{};  // row list, or null
     template <int IN_MT, int NB>
     NGP_DEV void operator()(uint32_t row0, uint32_t B, uint32_t in_dim, const f32x4 (&t)[NB][IN_MT]) const {
         const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
@@ -1049,6 +1097,7 @@ struct GiPairMajor {
         }
     }
 };
+using GiPairMajor = GiPairMajorT<const int32_t*>;
 
 #ifdef NGP_STAMPS  // diagnostic build only (tools/accum_stamps.py): per-wave phase clocks
 #define MSTAMP(slot) do { if (g_mlp_stamps && (threadIdx.x & 63) == 0) g_mlp_stamps[((size_t)(NH - 1) * 2048 + blockIdx.x * kBwdWaves + (threadIdx.x >> 6)) * 16 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -1371,7 +1420,23 @@ struct NerfBwdArgs {
     // of the next bin launch
     ngp_half* stash;
     uint32_t dw_rows_max;
+    // the join (k_nerf_bwd<.., JOIN>, ngp_nerf_backward_join_dw): instead of a
+    // finished list (rows / count null) the composite's per-ray lists: rays
+    // [N, 3] (a ray's first row in column 1), live_cnt [N] (16-byte aligned),
+    // ray_rows [M]. Every workgroup joins the entries of its own chunks into
+    // LDS and stores them to live_rows; workgroup 0 stores live_total.
+    const int32_t* join_rays;
+    const int32_t* join_cnt;
+    const int32_t* join_ray_rows;
+    uint32_t join_n;
+    int32_t* join_rows;
+    int32_t* join_total;
 };
+// The join takes every ray in one pass, 16 per thread; a workgroup's chunks
+// (32 list entries each) fill kJoinRounds rounds of one entry per thread.
+constexpr uint32_t kJoinRaysPerThread = 16, kJoinMaxRays = kJoinRaysPerThread * kBwdThreads;
+constexpr uint32_t kJoinRounds = 4, kJoinMaxChunks = kJoinRounds * kBwdThreads / (16 * kNB);
+constexpr size_t kJoinLdsBytes = (size_t)kJoinMaxChunks * 16 * kNB * 4 + 16;  // the row list + four wave totals
 
 template <int NHS, int NHC>
 struct NerfBwdLds {
@@ -1386,19 +1451,108 @@ struct NerfBwdLds {
     static constexpr size_t total = sigma_frags + LS::frag_bytes;
     static constexpr bool fits = total <= 160 * 1024;
 };
-template <int NHS, int NHC, bool DW>
+template <int NHS, int NHC, bool DW, bool JOIN = false>
 __global__ void __launch_bounds__(kBwdThreads)
 k_nerf_bwd(NerfBwdArgs a) {
     using LC = BwdLds<64, 1, NHC>;
     using LS = BwdLds<64, 1, NHS>;
     using NL = NerfBwdLds<NHS, NHC>;
     static_assert(NL::fits, "nerf backward LDS budget exceeded");
+    static_assert(!JOIN || DW, "the join runs in the kernel that holds both regimes");
+    static_assert(NL::total + kJoinLdsBytes <= 160 * 1024, "the joined row list must fit beside the passes' LDS");
+    static_assert((size_t)2 * kJoinMaxRays * 4 <= LC::tile_bytes, "the join's ray offsets lie in the colour pass's tiles");
     uint32_t B = a.B;
-    if (a.count) B = *a.count <= 0 ? 0u : min(B, (uint32_t)*a.count);
+    if constexpr (!JOIN)
+        if (a.count) B = *a.count <= 0 ? 0u : min(B, (uint32_t)*a.count);
     extern __shared__ half8 lds[];
     half8* sfr = reinterpret_cast<half8*>(reinterpret_cast<char*>(lds) + NL::sigma_frags);
     const uint32_t G = gridDim.x, b = blockIdx.x, w = threadIdx.x >> 6;
     const uint32_t tcall = a.timing && threadIdx.x == 0 ? a.timing[0] : 0u;  // requested early
+    // The join, first part: the list position of every ray and the list's
+    // length, from the per-ray counts (16-byte loads) and first rows, all
+    // requested together and before the colour image, so the rest of the join
+    // runs under that copy. Thread t sums rays 16 t .. 16 t + 15; each ray's
+    // position within its wave's rays and its first row lie in LDS (the colour
+    // pass's tile space, unused until the copy's barrier) and the four wave
+    // totals in a few words: LDS-only barriers.
+    constexpr int CPER = (LC::FRAGS * 64 + kBwdThreads - 1) / kBwdThreads;
+    [[maybe_unused]] half8 cimg[CPER];
+    [[maybe_unused]] int32_t* s_rows = nullptr;
+    [[maybe_unused]] uint32_t* s_pos = nullptr;
+    [[maybe_unused]] uint32_t wbase[kBwdWaves] = {};
+    if constexpr (JOIN) {
+        const uint32_t t = threadIdx.x, N = a.join_n, nfull = N / 4;
+        s_rows = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(lds) + NL::total);
+        uint32_t* s_wtot = reinterpret_cast<uint32_t*>(s_rows + kJoinMaxChunks * 16 * kNB);
+        s_pos = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds) + LC::frag_bytes);
+        uint32_t* s_src = s_pos + kJoinMaxRays;
+        const int4* cnt4 = reinterpret_cast<const int4*>(a.join_cnt);
+        int4 cv[4];
+        int32_t tail[3], src[kJoinRaysPerThread];
+        // Coalesced requests: count group q 256 + t (rays 4 (q 256 + t) .. + 3) and
+        // the first row of ray k 256 + t. (A thread reading its own 16 rays
+        // touched 64 cache lines per wave load: the kernel was 1 us longer,
+        // DESIGN.md section 1.) Whole groups of four counts only (launch-uniform
+        // test: a list of under four rays has none to read)
+        if (nfull) {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) cv[q] = cnt4[min(q * kBwdThreads + t, nfull - 1)];
+        } else {
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) cv[q] = int4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 3; ++k) tail[k] = a.join_cnt[min(4 * nfull + k, N - 1)];  // the last, partial group
+#pragma unroll
+        for (uint32_t k = 0; k < kJoinRaysPerThread; ++k)
+            src[k] = a.join_rays[(size_t)min(k * kBwdThreads + t, N - 1) * 3 + 1];
+        load_frags<LC::FRAGS, kBwdThreads>(a.color_image, cimg);
+        // ... into LDS by ray index (rays at or past N count 0), from where
+        // thread t takes rays 16 t .. 16 t + 15: a first LDS-only barrier
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+            const uint32_t g4 = q * kBwdThreads + t;
+            const int4 v = cv[q];
+            const int32_t x[4] = {g4 == nfull ? tail[0] : v.x, g4 == nfull ? tail[1] : v.y,
+                                  g4 == nfull ? tail[2] : v.z, g4 == nfull ? 0 : v.w};
+            uint32_t cc[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) cc[k] = 4 * g4 + k < N && x[k] > 0 ? (uint32_t)x[k] : 0u;
+            reinterpret_cast<uint4*>(s_pos)[g4] = uint4{cc[0], cc[1], cc[2], cc[3]};
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kJoinRaysPerThread; ++k) s_src[k * kBwdThreads + t] = (uint32_t)src[k];
+        lds_barrier();
+        uint32_t c[kJoinRaysPerThread], sum = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {
+            const uint4 v = reinterpret_cast<const uint4*>(s_pos)[4 * t + q];
+            c[4 * q] = v.x; c[4 * q + 1] = v.y; c[4 * q + 2] = v.z; c[4 * q + 3] = v.w;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kJoinRaysPerThread; ++k) sum += c[k];
+        const uint32_t incl = ngp_dpp::scan_incl_u32(sum);
+        uint32_t run = incl - sum;  // the thread's first position among its wave's rays
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) {  // (its own entries: no other thread reads them before the next barrier)
+            uint4 pv;
+            pv.x = run; run += c[4 * q];
+            pv.y = run; run += c[4 * q + 1];
+            pv.z = run; run += c[4 * q + 2];
+            pv.w = run; run += c[4 * q + 3];
+            reinterpret_cast<uint4*>(s_pos)[4 * t + q] = pv;
+        }
+        if ((t & 63) == 63) s_wtot[w] = incl;
+        lds_barrier();
+        uint32_t total = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)kBwdWaves; ++k) {
+            wbase[k] = total;
+            total += s_wtot[k];
+        }
+        if (b == 0 && t == 0) *a.join_total = (int32_t)total;
+        B = min(B, total);
+    }
     // this workgroup's chunks b, b + G, ...: n of them, the j-th in slot j % 4.
     // When the last round holds r = 1 or 2 chunks (2 or 3 of the 4 waves idle
     // for a whole chunk), they are split into 2r halves of 16 samples, one per
@@ -1419,9 +1573,11 @@ k_nerf_bwd(NerfBwdArgs a) {
     const uint32_t idle0 = n == 1 ? 2u : 3u;
     auto pre_of = [&]() {
         return [&]() {
-            copy_frags<LC::FRAGS, kBwdThreads>(lds, a.color_image);
-            if (!idle_copy) copy_frags<LS::FRAGS, kBwdThreads>(sfr, a.sigma_image);
-            __syncthreads();
+            if constexpr (!JOIN) {  // (the join has copied the images: below)
+                copy_frags<LC::FRAGS, kBwdThreads>(lds, a.color_image);
+                if (!idle_copy) copy_frags<LS::FRAGS, kBwdThreads>(sfr, a.sigma_image);
+                __syncthreads();
+            }
         };
     };
     auto idle_of = [&]() {
@@ -1435,28 +1591,83 @@ k_nerf_bwd(NerfBwdArgs a) {
     // (bit-identical g_h and g_enc), the dW operands stashed per chunk, one
     // barrier between the passes. The workgroups without a chunk leave.
     bool light = false;
-    if constexpr (DW) light = a.rows && a.dw_rows_max && B <= a.dw_rows_max;
+    if constexpr (DW) light = (JOIN || a.rows) && a.dw_rows_max && B <= a.dw_rows_max;
+    // live rows: the workgroups past the slab rows the reduce reads have no
+    // chunk and skip both passes (ngp_reduce::live_slab_rows)
+    const bool runs = light ? b < nch : !(JOIN || a.rows) || b < ngp_reduce::live_slab_rows((int32_t)B, G);
+    // The join, second part (the workgroups that run): list position p of an
+    // own chunk lies in the wave whose base is the last one <= p, in the ray
+    // with the last s_pos <= p - base there (a four-way search; rays without
+    // live rows share their successor's position and are passed over), and
+    // holds ray_rows[that ray's first row + the remainder]. Thread t takes
+    // entries t, t + 256, ... of the workgroup's 32 n; the loads are
+    // unconditional (an entry past the list reads position 0) and every one
+    // is requested before the image's registers go to LDS. The entries go to
+    // the LDS list the row maps read and to live_rows for the later launches:
+    // every chunk below the count belongs to exactly one workgroup that runs
+    // (chunk c to workgroup c % G < min(G, nch)). The copy's barrier publishes
+    // the list.
+    if constexpr (JOIN) if (runs) {
+        const uint32_t t = threadIdx.x, rounds = ngp_div_up(n * 16 * kNB, kBwdThreads);
+        const uint32_t* s_src = s_pos + kJoinMaxRays;
+        int32_t row[kJoinRounds];
+        uint32_t pos[kJoinRounds];
+#pragma unroll
+        for (uint32_t k = 0; k < kJoinRounds; ++k) {
+            pos[k] = kNoHalf;
+            row[k] = 0;
+            if (k < rounds) {  // workgroup-uniform
+                const uint32_t e = t + k * kBwdThreads, j = e / (16 * kNB);
+                const uint32_t p = (b + j * G) * 16 * kNB + (e & (16 * kNB - 1));
+                const bool ok = j < n && p < B;
+                const uint32_t pc = ok ? p : 0u;  // (a workgroup that runs a chunk has B > 0)
+                const uint32_t wv = (pc >= wbase[1] ? 1u : 0u) + (pc >= wbase[2] ? 1u : 0u) + (pc >= wbase[3] ? 1u : 0u);
+                const uint32_t rel = pc - (wv == 0 ? wbase[0] : wv == 1 ? wbase[1] : wv == 2 ? wbase[2] : wbase[3]);
+                const uint32_t ray0 = wv * 64 * kJoinRaysPerThread;
+                // (four-way steps: three independent LDS reads per round, 5 dependent rounds for 1024 rays)
+                uint32_t lo = 0;
+#pragma unroll
+                for (uint32_t q = 64 * kJoinRaysPerThread / 4; q > 0; q /= 4) {
+                    const uint32_t p1 = s_pos[ray0 + lo + q], p2 = s_pos[ray0 + lo + 2 * q], p3 = s_pos[ray0 + lo + 3 * q];
+                    lo += q * ((p1 <= rel ? 1u : 0u) + (p2 <= rel ? 1u : 0u) + (p3 <= rel ? 1u : 0u));
+                }
+                row[k] = a.join_ray_rows[s_src[ray0 + lo] + (rel - s_pos[ray0 + lo])];
+                if (ok) pos[k] = p;
+            }
+        }
+        store_frags<LC::FRAGS, kBwdThreads>(lds, cimg);
+#pragma unroll
+        for (uint32_t k = 0; k < kJoinRounds; ++k) {
+            if (pos[k] != kNoHalf) {
+                s_rows[t + k * kBwdThreads] = row[k];
+                a.join_rows[pos[k]] = row[k];
+            }
+        }
+        if (n == 0 && t == 0) s_rows[0] = 0;  // (the clamped reads of a workgroup that only writes its zero slab row)
+        if (!idle_copy) copy_frags<LS::FRAGS, kBwdThreads>(sfr, a.sigma_image);
+        __syncthreads();
+    }
+    auto passes = [&](auto rm) {
+    using RM = decltype(rm);
     if constexpr (DW) if (light) {
         if (b < nch) {
             constexpr uint32_t REC = (ngp_reduce::dw_net_units(NHC) + ngp_reduce::dw_net_units(NHS)) * 32u;
             bwd_phase<64, 1, NHC, true, true>(
                 lds, reinterpret_cast<ngp_half*>(reinterpret_cast<char*>(lds) + LC::frag_bytes),
-                reinterpret_cast<float*>(lds), a.g_color_out, a.color_in, InRowMajor{a.rows},
-                GiNerfGeo{a.g_h, a.rows}, true, nullptr, 0u, B, 32u, ActReLU{}, map_of(w), pre_of(), half_of(w),
+                reinterpret_cast<float*>(lds), a.g_color_out, a.color_in, InRowMajorT<RM>{rm},
+                GiNerfGeoT<RM>{a.g_h, rm}, true, nullptr, 0u, B, 32u, ActReLU{}, map_of(w), pre_of(), half_of(w),
                 idle_of(), a.stash, REC);
             bwd_phase<64, 1, NHS, false, true>(
                 sfr, reinterpret_cast<ngp_half*>(lds), reinterpret_cast<float*>(lds), a.g_h, a.enc,
-                InPairMajor{a.B, a.rows}, GiPairMajor{a.g_enc, a.B, a.rows}, true, nullptr, 0u, B, 32u, ActReLU{},
+                InPairMajorT<RM>{a.B, rm}, GiPairMajorT<RM>{a.g_enc, a.B, rm}, true, nullptr, 0u, B, 32u, ActReLU{},
                 map_of(kBwdWaves - 1 - w), []() {}, half_of(kBwdWaves - 1 - w), NoIdle{},
                 a.stash + (size_t)ngp_reduce::dw_net_units(NHC) * 32u, REC);
         }
     }
-    // live rows: the workgroups past the slab rows the reduce reads have no
-    // chunk and skip both passes (ngp_reduce::live_slab_rows)
-    if (!light && (!a.rows || b < ngp_reduce::live_slab_rows((int32_t)B, G))) {
+    if (!light && runs) {
     bwd_phase<64, 1, NHC, true, false>(lds, reinterpret_cast<ngp_half*>(reinterpret_cast<char*>(lds) + LC::frag_bytes),
-                          reinterpret_cast<float*>(lds), a.g_color_out, a.color_in, InRowMajor{a.rows},
-                          GiNerfGeo{a.g_h, a.rows},
+                          reinterpret_cast<float*>(lds), a.g_color_out, a.color_in, InRowMajorT<RM>{rm},
+                          GiNerfGeoT<RM>{a.g_h, rm},
                           true, a.slab_color, a.np_color, B, 32u, ActReLU{}, map_of(w), pre_of(), half_of(w),
                           idle_of());
     // the colour pass's geo grads (global stores of every wave) are complete
@@ -1465,9 +1676,14 @@ k_nerf_bwd(NerfBwdArgs a) {
     // row's stores need not land first
     lds_barrier();
     bwd_phase<64, 1, NHS, false, false>(sfr, reinterpret_cast<ngp_half*>(lds), reinterpret_cast<float*>(lds), a.g_h, a.enc,
-                          InPairMajor{a.B, a.rows}, GiPairMajor{a.g_enc, a.B, a.rows}, true, a.slab_sigma, a.np_sigma,
+                          InPairMajorT<RM>{a.B, rm}, GiPairMajorT<RM>{a.g_enc, a.B, rm}, true, a.slab_sigma, a.np_sigma,
                           B, 32u, ActReLU{}, map_of(kBwdWaves - 1 - w), []() {}, half_of(kBwdWaves - 1 - w));
     }
+    };
+    if constexpr (JOIN)
+        passes(LdsRows{s_rows, b, n, (float)G, 1.0f / (float)G});
+    else
+        passes(a.rows);
     if (a.timing && b < NGP_GRID_TIMING_MAX_WG / 4) {
         __syncthreads();
         if (threadIdx.x == 0)
@@ -1687,14 +1903,15 @@ int launch_bwd(const void* grad, const void* in, const void* w, const void* imag
                                       gw_dtype, defer, ws, count, st);
 }
 
-template <int NHS, int NHC, bool DW>
+template <int NHS, int NHC, bool DW, bool JOIN = false>
 int launch_nerf_bwd(const NerfBwdArgs& a, hipStream_t st) {
-    // all four depth pairs nerf_backward_impl dispatches fit (134 KB at most)
+    // all four depth pairs nerf_backward_impl dispatches fit (134 KB at most;
+    // the join's row list beside them)
     static_assert(NerfBwdLds<NHS, NHC>::fits, "nerf backward LDS budget exceeded");
     const uint32_t blocks = bwd_blocks(a.B);
     if (blocks == 0) return NGP_OK;
-    constexpr size_t lds_bytes = NerfBwdLds<NHS, NHC>::total;
-    hipLaunchKernelGGL((k_nerf_bwd<NHS, NHC, DW>), dim3(blocks), dim3(kBwdThreads), lds_bytes, st, a);
+    constexpr size_t lds_bytes = NerfBwdLds<NHS, NHC>::total + (JOIN ? kJoinLdsBytes : 0);
+    hipLaunchKernelGGL((k_nerf_bwd<NHS, NHC, DW, JOIN>), dim3(blocks), dim3(kBwdThreads), lds_bytes, st, a);
     return ngp_check_launch("nerf_backward");
 }
 
@@ -1805,7 +2022,8 @@ static int nerf_backward_impl(const void* g_color_out, const void* color_in, con
                               const int32_t* count, const int32_t* rows, uint32_t hidden_dim, uint32_t num_layers,
                               uint32_t hidden_dim_color, uint32_t num_layers_color, void* sigma_workspace,
                               size_t sigma_workspace_bytes, void* color_workspace, size_t color_workspace_bytes,
-                              uint32_t* timing, void* stream, void* dw_stash = nullptr, uint32_t dw_rows_max = 0) {
+                              uint32_t* timing, void* stream, void* dw_stash = nullptr, uint32_t dw_rows_max = 0,
+                              const NerfBwdArgs* join = nullptr) {
     NGP_REQUIRE(!rows || count, NGP_ERR_ARG, "nerf_backward_live: a row list needs its count");
     NGP_REQUIRE(hidden_dim == 64 && hidden_dim_color == 64, NGP_ERR_UNSUPPORTED,
                 "nerf_backward: 64-wide networks only on this build, got %u / %u", hidden_dim, hidden_dim_color);
@@ -1841,6 +2059,20 @@ static int nerf_backward_impl(const void* g_color_out, const void* color_in, con
     a.dw_rows_max = dw_stash ? dw_rows_max : 0u;
     hipStream_t st = ngp_stream(stream);
     const uint32_t key = (num_layers - 1) * 8 + (num_layers_color - 1);
+    if (join) {  // ... and joins the row list itself
+        a.join_rays = join->join_rays;
+        a.join_cnt = join->join_cnt;
+        a.join_ray_rows = join->join_ray_rows;
+        a.join_n = join->join_n;
+        a.join_rows = join->join_rows;
+        a.join_total = join->join_total;
+        switch (key) {
+            case 1 * 8 + 1: return launch_nerf_bwd<1, 1, true, true>(a, st);
+            case 1 * 8 + 2: return launch_nerf_bwd<1, 2, true, true>(a, st);
+            case 2 * 8 + 1: return launch_nerf_bwd<2, 1, true, true>(a, st);
+            default: return launch_nerf_bwd<2, 2, true, true>(a, st);
+        }
+    }
     if (dw_stash) {  // the kernel that holds both regimes
         switch (key) {
             case 1 * 8 + 1: return launch_nerf_bwd<1, 1, true>(a, st);
@@ -1888,6 +2120,51 @@ extern "C" int ngp_nerf_backward_live_dw(const void* g_color_out, const void* co
                               sigma_workspace_bytes, color_workspace, color_workspace_bytes, timing, stream, dw_stash,
                               dw_rows_limit(dw_stash_rows, dw_rows_max, B));
 }
+
+/* ngp_nerf_backward_live_dw over the composite's per-ray lists
+ * (ngp_nerf_composite_loss_lists): the launch joins the live-row list itself,
+ * each workgroup the entries of its own chunks, and leaves live_rows
+ * [0, live_total) and live_total as ngp_nerf_composite_loss_live would have.
+ * One pass holds kJoinMaxRays rays and kJoinMaxChunks chunks per workgroup:
+ * beyond either the call is refused (NGP_ERR_ARG) and nothing is launched;
+ * the caller then keeps the two-launch form. */
+extern "C" int ngp_nerf_backward_join_dw(const void* g_color_out, const void* color_in, const void* color_image,
+                                         void* g_h, const void* enc, const void* sigma_image, void* g_enc,
+                                         uint32_t B, const int32_t* rays, uint32_t N, const int32_t* live_cnt,
+                                         const int32_t* ray_rows, int32_t* live_rows, int32_t* live_total,
+                                         uint32_t hidden_dim, uint32_t num_layers, uint32_t hidden_dim_color,
+                                         uint32_t num_layers_color, void* sigma_workspace,
+                                         size_t sigma_workspace_bytes, void* color_workspace,
+                                         size_t color_workspace_bytes, uint32_t* timing, void* dw_stash,
+                                         uint32_t dw_stash_rows, uint32_t dw_rows_max, void* stream) {
+    NGP_REQUIRE(rays && live_cnt && ray_rows && live_rows && live_total, NGP_ERR_ARG,
+                "nerf_backward_join_dw: null rays [N,3] / live_cnt [N] / ray_rows [M] / live_rows [M] / live_total");
+    NGP_REQUIRE((reinterpret_cast<uintptr_t>(live_cnt) & 15) == 0, NGP_ERR_ARG,
+                "nerf_backward_join_dw: live_cnt must be 16-byte aligned");
+    NGP_REQUIRE(dw_stash, NGP_ERR_ARG, "nerf_backward_join_dw: null stash");
+    NGP_REQUIRE(N <= kJoinMaxRays, NGP_ERR_ARG, "nerf_backward_join_dw: at most %u rays in one pass, got %u",
+                kJoinMaxRays, N);
+    NGP_REQUIRE(B == 0 || ngp_div_up(ngp_div_up(B, ngp_reduce::kBwdChunkRows), bwd_blocks(B)) <= kJoinMaxChunks,
+                NGP_ERR_ARG, "nerf_backward_join_dw: at most %u chunks per workgroup, B = %u", kJoinMaxChunks, B);
+    if (N == 0 || B == 0) {  // no rays or no rows: an empty list
+        if (hipMemsetAsync(live_total, 0, sizeof(int32_t), ngp_stream(stream)) != hipSuccess)
+            return ngp_set_error(NGP_ERR_HIP, "nerf_backward_join_dw: memset failed");
+        return NGP_OK;
+    }
+    NerfBwdArgs j{};
+    j.join_rays = rays;
+    j.join_cnt = live_cnt;
+    j.join_ray_rows = ray_rows;
+    j.join_n = N;
+    j.join_rows = live_rows;
+    j.join_total = live_total;
+    return nerf_backward_impl(g_color_out, color_in, color_image, g_h, enc, sigma_image, g_enc, B, nullptr, nullptr,
+                              hidden_dim, num_layers, hidden_dim_color, num_layers_color, sigma_workspace,
+                              sigma_workspace_bytes, color_workspace, color_workspace_bytes, timing, stream, dw_stash,
+                              dw_rows_limit(dw_stash_rows, dw_rows_max, B), &j);
+}
+
+extern "C" uint32_t ngp_nerf_backward_join_max_rays(void) { return kJoinMaxRays; }
 
 // The product job of the two networks of ngp_nerf_backward_live_dw (network 0
 // the sigma network, 1 the colour network, as the reduce's arguments list them).

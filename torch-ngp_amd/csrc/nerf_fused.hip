@@ -928,22 +928,24 @@ extern "C" int ngp_nerf_composite_loss(const float* sigma, const void* color_out
     return ngp_check_launch("nerf_composite_loss");
 }
 
-extern "C" int ngp_nerf_composite_loss_live(const float* sigma, const void* color_out, const void* h_sigma,
-                                            const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
-                                            float T_thresh, float density_scale, const float* gt,
-                                            uint32_t gt_channels, const float* bg, void* state,
-                                            void* grad_color_out, void* grad_h_sigma, float* out_image,
-                                            float* out_ws, float* loss_ray, int32_t* ray_rows, int32_t* live_cnt,
-                                            int32_t* live_rows, int32_t* live_total, void* stream) {
+// compact: the list's join as the second launch (k_live_compact); otherwise the
+// per-ray lists are the output (ngp_nerf_composite_loss_lists)
+static int composite_loss_live_impl(const float* sigma, const void* color_out, const void* h_sigma,
+                                    const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                    float T_thresh, float density_scale, const float* gt, uint32_t gt_channels,
+                                    const float* bg, void* state, void* grad_color_out, void* grad_h_sigma,
+                                    float* out_image, float* out_ws, float* loss_ray, int32_t* ray_rows,
+                                    int32_t* live_cnt, int32_t* live_rows, int32_t* live_total, bool compact,
+                                    void* stream) {
     NGP_REQUIRE(loss_ray, NGP_ERR_ARG, "composite_loss_live: loss_ray [N] buffer required");
     NGP_REQUIRE(gt_channels == 3 || gt_channels == 4, NGP_ERR_ARG, "composite_loss_live: gt must be RGB or RGBA");
-    NGP_REQUIRE(ray_rows && live_cnt && live_rows && live_total, NGP_ERR_ARG,
+    NGP_REQUIRE(ray_rows && live_cnt && (!compact || (live_rows && live_total)), NGP_ERR_ARG,
                 "composite_loss_live: null ray_rows [M] / live_cnt [N] / live_rows [M] / live_total");
     NGP_REQUIRE((reinterpret_cast<uintptr_t>(live_cnt) & 15) == 0, NGP_ERR_ARG,
                 "composite_loss_live: live_cnt must be 16-byte aligned");
     hipStream_t st = ngp_stream(stream);
     if (N == 0) {
-        if (hipMemsetAsync(live_total, 0, sizeof(int32_t), st) != hipSuccess)
+        if (compact && hipMemsetAsync(live_total, 0, sizeof(int32_t), st) != hipSuccess)
             return ngp_set_error(NGP_ERR_HIP, "composite_loss_live: memset failed");
         return NGP_OK;
     }
@@ -957,10 +959,42 @@ extern "C" int ngp_nerf_composite_loss_live(const float* sigma, const void* colo
         sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
         static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
         out_ws, loss_ray, ray_rows, live_cnt, DepthArgs{});
-    k_live_compact<<<ngp_div_up(N, kLiveRaysPerBlock), kLiveThreads, 0, st>>>(rays, live_cnt, ray_rows, N, live_rows,
-                                                                              live_total);
+    if (compact)
+        k_live_compact<<<ngp_div_up(N, kLiveRaysPerBlock), kLiveThreads, 0, st>>>(rays, live_cnt, ray_rows, N,
+                                                                                  live_rows, live_total);
     return ngp_check_launch("nerf_composite_loss_live");
 }
+
+extern "C" int ngp_nerf_composite_loss_live(const float* sigma, const void* color_out, const void* h_sigma,
+                                            const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                            float T_thresh, float density_scale, const float* gt,
+                                            uint32_t gt_channels, const float* bg, void* state,
+                                            void* grad_color_out, void* grad_h_sigma, float* out_image,
+                                            float* out_ws, float* loss_ray, int32_t* ray_rows, int32_t* live_cnt,
+                                            int32_t* live_rows, int32_t* live_total, void* stream) {
+    return composite_loss_live_impl(sigma, color_out, h_sigma, deltas, rays, M, N, T_thresh, density_scale, gt,
+                                    gt_channels, bg, state, grad_color_out, grad_h_sigma, out_image, out_ws,
+                                    loss_ray, ray_rows, live_cnt, live_rows, live_total, true, stream);
+}
+
+extern "C" int ngp_nerf_composite_loss_lists(const float* sigma, const void* color_out, const void* h_sigma,
+                                             const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                             float T_thresh, float density_scale, const float* gt,
+                                             uint32_t gt_channels, const float* bg, void* state,
+                                             void* grad_color_out, void* grad_h_sigma, float* out_image,
+                                             float* out_ws, float* loss_ray, int32_t* ray_rows, int32_t* live_cnt,
+                                             void* stream) {
+    return composite_loss_live_impl(sigma, color_out, h_sigma, deltas, rays, M, N, T_thresh, density_scale, gt,
+                                    gt_channels, bg, state, grad_color_out, grad_h_sigma, out_image, out_ws,
+                                    loss_ray, ray_rows, live_cnt, nullptr, nullptr, false, stream);
+}
+
+static int composite_loss_depth_impl(const float* sigma, const void* color_out, const void* h_sigma,
+                                     const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                     float T_thresh, float density_scale, const float* gt, uint32_t gt_channels,
+                                     const float* bg, void* state, void* grad_color_out, void* grad_h_sigma,
+                                     float* out_image, float* out_ws, float* loss_ray,
+                                     const ngp_depth_loss_job* job, bool compact, void* stream);
 
 extern "C" int ngp_nerf_composite_loss_depth(const float* sigma, const void* color_out, const void* h_sigma,
                                              const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
@@ -969,19 +1003,46 @@ extern "C" int ngp_nerf_composite_loss_depth(const float* sigma, const void* col
                                              void* grad_color_out, void* grad_h_sigma, float* out_image,
                                              float* out_ws, float* loss_ray, const ngp_depth_loss_job* job,
                                              void* stream) {
+    return composite_loss_depth_impl(sigma, color_out, h_sigma, deltas, rays, M, N, T_thresh, density_scale, gt,
+                                     gt_channels, bg, state, grad_color_out, grad_h_sigma, out_image, out_ws,
+                                     loss_ray, job, true, stream);
+}
+
+extern "C" int ngp_nerf_composite_loss_depth_lists(const float* sigma, const void* color_out, const void* h_sigma,
+                                                   const float* deltas, const int32_t* rays, uint32_t M,
+                                                   uint32_t N, float T_thresh, float density_scale,
+                                                   const float* gt, uint32_t gt_channels, const float* bg,
+                                                   void* state, void* grad_color_out, void* grad_h_sigma,
+                                                   float* out_image, float* out_ws, float* loss_ray,
+                                                   const ngp_depth_loss_job* job, void* stream) {
+    NGP_REQUIRE(job && job->ray_rows && job->live_cnt, NGP_ERR_ARG,
+                "composite_loss_depth_lists: the job's ray_rows [M] and live_cnt [N] are required");
+    return composite_loss_depth_impl(sigma, color_out, h_sigma, deltas, rays, M, N, T_thresh, density_scale, gt,
+                                     gt_channels, bg, state, grad_color_out, grad_h_sigma, out_image, out_ws,
+                                     loss_ray, job, false, stream);
+}
+
+// compact false (.._depth_lists): the job's live_rows / live_total are not used
+static int composite_loss_depth_impl(const float* sigma, const void* color_out, const void* h_sigma,
+                                     const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                     float T_thresh, float density_scale, const float* gt, uint32_t gt_channels,
+                                     const float* bg, void* state, void* grad_color_out, void* grad_h_sigma,
+                                     float* out_image, float* out_ws, float* loss_ray,
+                                     const ngp_depth_loss_job* job, bool compact, void* stream) {
     NGP_REQUIRE(job, NGP_ERR_ARG, "composite_loss_depth: null job");
     NGP_REQUIRE(loss_ray, NGP_ERR_ARG, "composite_loss_depth: loss_ray [N] buffer required");
     NGP_REQUIRE(gt_channels == 3 || gt_channels == 4, NGP_ERR_ARG, "composite_loss_depth: gt must be RGB or RGBA");
     NGP_REQUIRE(job->gt_depth || job->depth_weight == 0.0f, NGP_ERR_ARG,
                 "composite_loss_depth: a depth weight needs the gt_depth [N] buffer");
-    const bool live = job->ray_rows || job->live_cnt || job->live_rows || job->live_total;
-    NGP_REQUIRE(!live || (job->ray_rows && job->live_cnt && job->live_rows && job->live_total), NGP_ERR_ARG,
+    const bool live = job->ray_rows || job->live_cnt || (compact && (job->live_rows || job->live_total));
+    NGP_REQUIRE(!live || (job->ray_rows && job->live_cnt && (!compact || (job->live_rows && job->live_total))),
+                NGP_ERR_ARG,
                 "composite_loss_depth: ray_rows [M] / live_cnt [N] / live_rows [M] / live_total: all or none");
     NGP_REQUIRE(!live || (reinterpret_cast<uintptr_t>(job->live_cnt) & 15) == 0, NGP_ERR_ARG,
                 "composite_loss_depth: live_cnt must be 16-byte aligned");
     hipStream_t st = ngp_stream(stream);
     if (N == 0) {
-        if (live && hipMemsetAsync(job->live_total, 0, sizeof(int32_t), st) != hipSuccess)
+        if (live && compact && hipMemsetAsync(job->live_total, 0, sizeof(int32_t), st) != hipSuccess)
             return ngp_set_error(NGP_ERR_HIP, "composite_loss_depth: memset failed");
         return NGP_OK;
     }
@@ -997,7 +1058,7 @@ extern "C" int ngp_nerf_composite_loss_depth(const float* sigma, const void* col
         sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
         static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
         out_ws, loss_ray, job->ray_rows, job->live_cnt, da);
-    if (live)
+    if (live && compact)
         k_live_compact<<<ngp_div_up(N, kLiveRaysPerBlock), kLiveThreads, 0, st>>>(rays, job->live_cnt, job->ray_rows,
                                                                                   N, job->live_rows, job->live_total);
     return ngp_check_launch("nerf_composite_loss_depth");

@@ -92,6 +92,12 @@ def _vp_array(ptrs):
 #                 this many live rows form the MLP weight gradients in the bin
 #                 launch, from operands the backward stashes, instead of in the
 #                 backward itself: the same bits (0: always in the backward)
+#   join_in_bwd   with dw_rows: the MLP backward joins the composite's per-ray
+#                 live-row lists itself (ngp_nerf_backward_join_dw), each workgroup
+#                 the entries of its own chunks, instead of a launch of its own
+#                 after the composite: the same list and the same bits, one launch
+#                 less (kept off where the kernel refuses the shape: more than
+#                 4096 rays or 262144 rows)
 #   dp_graph      data parallel over RCCL: the whole step is one graph
 #   density_sort  partial density updates draw their cells as order statistics, in
 #                 Morton order (False: the counter-RNG draws in draw order)
@@ -106,7 +112,7 @@ def _vp_array(ptrs):
 DEFAULT_OPTIONS = dict(table16=False, split_head=False, split_reduce=False, split_fwd=False, split_bwd=False,
                        march_adam=True, tail_in_fwd=True, emit_inline=True, draw_ahead=True, live_rows=True,
                        dp_graph=True, density_sort=True, sparse_exchange=False, exact_reduce=False,
-                       density_run_max=False, dw_rows=8192)
+                       density_run_max=False, dw_rows=8192, join_in_bwd=True)
 
 
 def perm_mult(n):
@@ -531,6 +537,10 @@ class FusedTrainer:
             self._dw_cap = min(M, (self._dw_rows + 31) // 32 * 32, 32 * wgs)
             self._dw_stash = z(int(nat.lib().ngp_nerf_dw_stash_bytes(self._dw_cap, self.sig_net.num_layers,
                                                                      self.col_net.num_layers)), dtype=torch.uint8)
+        # ... with the list joined by the backward itself (join_in_bwd) where its one
+        # pass holds the shape; the per-ray lists are per-step scratch like the list
+        self._join = bool(opts["join_in_bwd"] and self._dw_rows and M <= 32 * 32 * 256
+                          and N <= int(nat.lib().ngp_nerf_backward_join_max_rays()))
         if self._loss_job is not None and self._live:
             # (a batch's composite runs its live form exactly when it draws ahead: see _network)
             lb, lj = self._live_bufs, self._loss_job
@@ -1114,11 +1124,19 @@ class FusedTrainer:
         if self._loss_job is not None:
             # the depth-supervised loss (and its weights): one entry for both row forms
             job = self._loss_job_live if live else self._loss_job
-            chk(lib.ngp_nerf_composite_loss_depth(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
+            entry = lib.ngp_nerf_composite_loss_depth_lists if live and self._join else lib.ngp_nerf_composite_loss_depth
+            chk(entry(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
+                      P(self.rays), M, N, self.T_thresh, float(m.density_scale),
+                      P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
+                      P(self.g_h), img_out, ws_out, P(self.loss_ray), ctypes.byref(job), s),
+                "composite_loss_depth")
+        elif live and self._join:
+            chk(lib.ngp_nerf_composite_loss_lists(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                                   P(self.rays), M, N, self.T_thresh, float(m.density_scale),
                                                   P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
-                                                  P(self.g_h), img_out, ws_out, P(self.loss_ray), ctypes.byref(job), s),
-                "composite_loss_depth")
+                                                  P(self.g_h), img_out, ws_out, P(self.loss_ray), P(lv["ray_rows"]),
+                                                  P(lv["cnt"]), s),
+                "composite_loss_lists")
         elif live:
             chk(lib.ngp_nerf_composite_loss_live(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
                                                  P(self.rays), M, N, self.T_thresh, float(m.density_scale),
@@ -1143,7 +1161,16 @@ class FusedTrainer:
             self._background_backward()
         if self._one_bwd:  # both networks' backward in one launch (ngp_nerf_backward)
             timing = P(self.grid_ws) + self._grid_timing_at if self._grid_timing_at else None
-            if live and self._dw_rows:
+            if live and self._join:
+                chk(lib.ngp_nerf_backward_join_dw(P(self.g_color_out), P(self.color_in), P(img[1]), P(self.g_h),
+                                                  P(self.enc_out), P(img[0]), P(self.g_enc), M, P(self.rays), N,
+                                                  P(lv["cnt"]), P(lv["ray_rows"]), P(lv["rows"]), P(lv["total"]),
+                                                  sn.hidden_dim, sn.num_layers, cn.hidden_dim, cn.num_layers,
+                                                  P(self.mlp_ws[0]), self.mlp_ws[0].numel(), P(self.mlp_ws[1]),
+                                                  self.mlp_ws[1].numel(), timing, P(self._dw_stash), self._dw_cap,
+                                                  self._dw_rows, s),
+                    "nerf_backward_join_dw")
+            elif live and self._dw_rows:
                 chk(lib.ngp_nerf_backward_live_dw(P(self.g_color_out), P(self.color_in), P(img[1]), P(self.g_h),
                                                   P(self.enc_out), P(img[0]), P(self.g_enc), M, P(lv["rows"]),
                                                   P(lv["total"]), sn.hidden_dim, sn.num_layers, cn.hidden_dim,
