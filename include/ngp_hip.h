@@ -323,6 +323,16 @@ int ngp_adam_step(float* params, const void* grads, int32_t grad_dtype, float* e
                   float* exp_avg_sq, size_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int32_t step, float grad_scale, void* stream);
 
+/* Exponential moving average of a flat parameter vector, torch_ema's
+ * ExponentialMovingAverage.update() in one pass:
+ *   shadow[i] = shadow[i] - one_minus_decay * (shadow[i] - param[i])
+ * in fp32, in exactly that order (tmp = s - p; tmp *= 1 - decay; s -= tmp),
+ * without contraction: torch's three operations bit for bit. 16-byte accesses
+ * in a grid-stride loop, the last n % 4 elements one by one; 12 B per
+ * parameter. n == 0: nothing is launched, NGP_OK. Null or not 16-byte aligned
+ * pointers: NGP_ERR_ARG. */
+int ngp_ema_update(float* shadow, const float* param, uint64_t n, float one_minus_decay, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Fused train step (DESIGN.md "fused step"). No reference counterpart as C
  * functions: together they replace the elementwise torch glue of one
@@ -1097,6 +1107,30 @@ int ngp_frame_begin(const float* poses, uint32_t n_poses, uint32_t pose_index, c
 int ngp_frame_finish(uint32_t H, uint32_t W, const float* image, const float* weights_sum, const float* depth,
                      const float* nears, const float* fars, float bg_color, uint8_t* rgb8, uint8_t* depth8,
                      float* image_out, float* depth_out, void* stream);
+
+/* The validation pass: one launch after the loop has ended, in place of
+ * ngp_frame_finish. Per pixel p and channel j,
+ *   c  = image[p][j] + (1 - weights_sum[p]) * bg_color      (ngp_frame_finish's c)
+ *   gt = pixel p of image `pose_index` of src->pixels [n, H, W, channels],
+ *        decoded as the training draw decodes it (uint8: v / 255, a true
+ *        division; float32 as stored), RGBA blended on white in fp32:
+ *        rgb * a + (1 - a)                                   (nerf.eval.ground_truth)
+ *   d  = c - gt, d * d in fp32 without contraction,
+ * and sse_out[pose_index] (double) = the sum of all 3 H W squares, added in
+ * double: each thread adds the squares of its 4-pixel runs in pixel order, a
+ * workgroup adds its threads in a fixed tree and stores one partial, and the
+ * workgroup that finishes last (an integer ticket) adds the partials in index
+ * order. No floating-point atomics: the sum depends on H * W alone and is
+ * the same from run to run. A non-finite c makes the sum non-finite. Only
+ * pixels, channels and dtype of src are read (its checks are the draw's);
+ * the caller guarantees pose_index < n. The partials and the ticket are the
+ * library's: one call at a time per device (calls on one stream are); the
+ * entry clears the ticket on the stream before the launch, so a call does
+ * not depend on how an earlier one ended. image
+ * and weights_sum 16-byte aligned, sse_out 8-byte aligned. Null buffers, a
+ * bad source, H * W outside [1, 2^28), misalignment: NGP_ERR_ARG. */
+int ngp_frame_sse(uint32_t H, uint32_t W, const float* image, const float* weights_sum, float bg_color,
+                  const ngp_image_source* src, uint32_t pose_index, double* sse_out, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Background model (the reference's --bg_radius, nerf/network.py:107-129,  */

@@ -10,8 +10,11 @@
 //                   zeroed noises, and everything ngp_render_init initialises
 //   k_frame_finish  one launch after it: background blend, depth
 //                   normalisation and the uint8 quantisation
+//   k_frame_sse     or, in its place, the validation pass: the blended colour
+//                   against the view's ground-truth image, the squared error
+//                   summed in double on the device
 //
-// Both make one pass over the pixels and are bound by memory. A thread owns 4
+// All make one pass over the pixels and are bound by memory. A thread owns 4
 // consecutive pixels, so every [N] array moves as one 16-byte access per
 // thread, every [N, 3] array as three, the 12 colour bytes as three dwords and
 // the 4 depth bytes as one. The last N % 4 pixels of a frame go element by
@@ -164,6 +167,109 @@ k_frame_finish(uint32_t N, const float* __restrict__ image, const float* __restr
     if (depth_out) put(depth_out + p0, z, full, cnt);
 }
 
+// The validation pass: the squared error of a rendered view
+// against its ground-truth image, summed on the device. A workgroup's threads
+// take 4-pixel runs in a grid-stride loop, each thread adds its squares up in
+// double in pixel order, the workgroup adds its threads' sums in a fixed tree
+// and stores one partial; the workgroup that finishes last (an integer ticket)
+// adds the partials in index order. Nothing in the sum depends on timing, so
+// it is the same from run to run. The partials and the ticket are the
+// library's own (one pass at a time per device: calls are issued in stream
+// order on one stream); the entry clears the ticket on the stream before every
+// launch, so a pass does not depend on how an earlier one ended.
+constexpr uint32_t kSseMaxBlocks = 1024;
+__device__ double g_sse_partial[kSseMaxBlocks];
+__device__ uint32_t g_sse_ticket;
+
+struct GroundTruth {
+    const void* pixels;  // [n_poses, H, W, channels], already offset to the pose
+    uint32_t channels;
+    int32_t dtype;
+};
+
+// Pixel p of the view as nerf.eval.ground_truth gives it: ngp_head::image_target's
+// decode (uint8: v / 255, a true division; float32 as stored), RGBA blended on
+// white, rgb * a + (1 - a), in float32.
+NGP_DEV void ground_truth(const GroundTruth& gt, uint32_t p, float (&c)[3]) {
+    float a = 1.0f;
+    if (gt.dtype == NGP_DTYPE_U8) {
+        uint32_t c0, c1, c2, c3 = 255u;
+        if (gt.channels == 4) {
+            const uint32_t w = static_cast<const uint32_t*>(gt.pixels)[p];
+            c0 = w & 255u; c1 = (w >> 8) & 255u; c2 = (w >> 16) & 255u; c3 = w >> 24;
+        } else {
+            const uint8_t* q = static_cast<const uint8_t*>(gt.pixels) + (size_t)p * 3;
+            c0 = q[0]; c1 = q[1]; c2 = q[2];
+        }
+        c[0] = (float)c0 / 255.0f; c[1] = (float)c1 / 255.0f; c[2] = (float)c2 / 255.0f;
+        if (gt.channels == 4) a = (float)c3 / 255.0f;
+    } else if (gt.channels == 4) {
+        const float4 v = static_cast<const float4*>(gt.pixels)[p];
+        c[0] = v.x; c[1] = v.y; c[2] = v.z; a = v.w;
+    } else {
+        const float* q = static_cast<const float*>(gt.pixels) + (size_t)p * 3;
+        c[0] = q[0]; c[1] = q[1]; c[2] = q[2];
+    }
+    if (gt.channels == 4) {
+        const float w = 1.0f - a;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c[j] = c[j] * a + w;
+    }
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_frame_sse(uint32_t N, const float* __restrict__ image, const float* __restrict__ weights_sum, float bg,
+            GroundTruth gt, double* __restrict__ sse_out) {
+    __shared__ double s_sum[kThreads];
+    __shared__ uint32_t s_last;
+    double acc = 0.0;
+    const uint32_t stride = gridDim.x * kThreads * kPix;
+    for (uint32_t p0 = (blockIdx.x * kThreads + threadIdx.x) * kPix; p0 < N; p0 += stride) {
+        const uint32_t cnt = min(kPix, N - p0);
+        const bool full = cnt == kPix;
+        float im[kPix * 3], ws[kPix];
+        get(image + (size_t)p0 * 3, im, full, cnt * 3);
+        get(weights_sum + p0, ws, full, cnt);
+#pragma unroll
+        for (uint32_t k = 0; k < kPix; ++k) {
+            if (k >= cnt) break;
+            float t[3];
+            ground_truth(gt, p0 + k, t);
+            const float w = (1.0f - ws[k]) * bg;  // k_frame_finish's blend
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float d = (im[k * 3 + j] + w) - t[j];
+                acc += (double)(d * d);
+            }
+        }
+    }
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t o = kThreads / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&g_sse_partial[blockIdx.x], s_sum[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        s_last = atomicAdd(&g_sse_ticket, 1u) == gridDim.x - 1u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    // the last workgroup: partial b to thread b % 256 in ascending b, then the same tree
+    acc = 0.0;
+    for (uint32_t b = threadIdx.x; b < gridDim.x; b += kThreads)
+        acc += __hip_atomic_load(&g_sse_partial[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t o = kThreads / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *sse_out = s_sum[0];
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int check_frame_size(uint32_t H, uint32_t W, const char* who) {
@@ -215,4 +321,27 @@ extern "C" int ngp_frame_finish(uint32_t H, uint32_t W, const float* image, cons
     k_frame_finish<<<ngp_div_up(ngp_div_up(N, kPix), kThreads), kThreads, 0, ngp_stream(stream)>>>(
         N, image, weights_sum, depth, nears, fars, bg_color, rgb8, depth8, image_out, depth_out);
     return ngp_check_launch("frame_finish");
+}
+
+extern "C" int ngp_frame_sse(uint32_t H, uint32_t W, const float* image, const float* weights_sum, float bg_color,
+                             const ngp_image_source* src, uint32_t pose_index, double* sse_out, void* stream) {
+    if (int e = check_frame_size(H, W, "frame_sse")) return e;
+    if (int e = ngp_head::check_image_source(src, "frame_sse")) return e;
+    NGP_REQUIRE(image && weights_sum && sse_out, NGP_ERR_ARG, "frame_sse: null buffer");
+    NGP_REQUIRE(aligned16(image) && aligned16(weights_sum) && (reinterpret_cast<uintptr_t>(sse_out) & 7u) == 0,
+                NGP_ERR_ARG, "frame_sse: float buffers must be 16-byte aligned, sse_out 8-byte aligned");
+    const uint32_t N = H * W;
+    const size_t px_bytes = (size_t)src->channels * (src->dtype == NGP_DTYPE_F32 ? 4 : 1);
+    const GroundTruth gt{static_cast<const char*>(src->pixels) + (size_t)pose_index * N * px_bytes, src->channels,
+                         src->dtype};
+    const uint32_t want = ngp_div_up(ngp_div_up(N, kPix), kThreads);
+    const uint32_t blocks = want < kSseMaxBlocks ? want : kSseMaxBlocks;  // a function of N alone: the sum's order
+    // the ticket starts at 0 whatever an earlier pass left (one that was aborted, say)
+    void* ticket = nullptr;
+    NGP_REQUIRE(hipGetSymbolAddress(&ticket, HIP_SYMBOL(g_sse_ticket)) == hipSuccess &&
+                    hipMemsetAsync(ticket, 0, sizeof(uint32_t), ngp_stream(stream)) == hipSuccess,
+                NGP_ERR_HIP, "frame_sse: could not clear the ticket");
+    k_frame_sse<<<blocks, kThreads, 0, ngp_stream(stream)>>>(N, image, weights_sum, bg_color, gt,
+                                                             sse_out + pose_index);
+    return ngp_check_launch("frame_sse");
 }

@@ -26,9 +26,19 @@ the end of a training run. The frames are made on the device (nerf/frames.py).
 :107-129): what lies outside the box is learned as a colour per direction on
 the sphere of radius R (a 2-D hash grid and a small MLP), trained against the
 white-blended targets, and rendered in the evaluation and the frames.
+--ema_decay D keeps the reference's exponential moving average of the
+parameters (torch_ema, Trainer(ema_decay=0.95), main_nerf.py:219), updated at
+the end of every epoch of len(train) steps (nerf/utils.py:1051-1052); the
+evaluation, the frames and the best checkpoint then use the averaged weights,
+as the reference's do, and ngp.pth carries them as `ema`. --eval_interval E
+validates on the device every E epochs (nerf.eval.Validator over the val
+split) and keeps the best model in <workspace>/checkpoints/ngp_best.pth
+(--test --ckpt best renders it). --resume continues from
+<workspace>/checkpoints/ngp.pth (or --ckpt PATH) to --iters. DESIGN.md
+section 16.
 
 Not here: patch sampling, --color_space linear, more than one
-image per batch, video files, resuming training from a checkpoint."""
+image per batch, video files."""
 import argparse
 import math
 import os
@@ -76,10 +86,21 @@ def get_parser():
     p.add_argument("--save_mesh", action="store_true", help="write <workspace>/meshes/ngp.ply after the evaluation")
     p.add_argument("--mesh_resolution", type=int, default=256, help="lattice points per axis of the mesh's volume")
     p.add_argument("--mesh_threshold", type=float, default=10, help="density at which the surface is drawn")
+    # EMA, validation while training, resuming (the reference's Trainer(ema_decay=0.95, eval_interval=...),
+    # main_nerf.py:219, and its load_checkpoint on start, nerf/utils.py:410-432)
+    p.add_argument("--ema_decay", type=float, default=None,
+                   help="keep an exponential moving average of the parameters with this decay, updated every epoch, "
+                        "and evaluate / save the best model with it (the reference trains with 0.95); default: off")
+    p.add_argument("--eval_interval", type=int, default=0,
+                   help="validate every this many epochs (an epoch is one step per training view) and keep the best "
+                        "model in <workspace>/checkpoints/ngp_best.pth; 0: evaluate only at the end")
+    p.add_argument("--resume", action="store_true",
+                   help="continue training from <workspace>/checkpoints/ngp.pth (or --ckpt PATH) up to --iters")
     # test mode (the reference's --test / --ckpt and its trainer.test, main_nerf.py:188 / :239)
     p.add_argument("--test", action="store_true", help="test mode: load a checkpoint and write the test frames")
     p.add_argument("--ckpt", type=str, default="latest",
-                   help="checkpoint --test loads; latest: <workspace>/checkpoints/ngp.pth")
+                   help="checkpoint --test (or --resume) loads; latest: <workspace>/checkpoints/ngp.pth, "
+                        "best: <workspace>/checkpoints/ngp_best.pth")
     p.add_argument("--test_frames", type=int, default=10,
                    help="steps of the interpolated camera path when the scene has no transforms_test.json")
     p.add_argument("--write_frames", action="store_true",
@@ -117,9 +138,15 @@ def _test_path(opt, train, dev, data_args):
     return poses, train.H, train.W, train.intrinsics, f"poses between training views {a} and {b}"
 
 
-def _write_test_frames(opt, model, train, dev, data_args):
+def _ckpt_path(opt):
+    name = {"latest": "ngp.pth", "best": "ngp_best.pth"}.get(opt.ckpt)
+    return os.path.join(opt.workspace, "checkpoints", name) if name else opt.ckpt
+
+
+def _write_test_frames(opt, model, train, dev, data_args, source=None):
     """trainer.test (nerf/utils.py:743-796): every test pose rendered in eval
-    mode on a white background, written under <workspace>/results."""
+    mode on a white background, written under <workspace>/results. source: the
+    weights to render instead of the model's own (the EMA's)."""
     import torch
 
     from nerf.frames import FrameRenderer, write_frames
@@ -127,7 +154,7 @@ def _write_test_frames(opt, model, train, dev, data_args):
     was_training = model.training
     model.eval()
     fr = FrameRenderer(model, H, W, intrinsics, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma, bg_color=1.0)
-    fr.load_weights()
+    fr.load_weights(source)
     fr.capture()
     fr.set_poses(poses)
     out_dir = os.path.join(opt.workspace, "results")
@@ -147,7 +174,7 @@ def _test(opt, dev, bound, data_args):
 
     from nerf import mesh
     from nerf.network_ff import NeRFNetwork
-    ckpt = os.path.join(opt.workspace, "checkpoints", "ngp.pth") if opt.ckpt == "latest" else opt.ckpt
+    ckpt = _ckpt_path(opt)
     if not os.path.exists(ckpt):
         sys.exit(f"[main_nerf] --test: no checkpoint at {ckpt} (train first, or name one with --ckpt)")
     state = torch.load(ckpt, map_location="cpu", weights_only=False)
@@ -157,9 +184,15 @@ def _test(opt, dev, bound, data_args):
     model.load_state_dict(state.get("model", state), strict=False)
     model.mean_count = state.get("mean_count", model.mean_count)
     model.mean_density = state.get("mean_density", model.mean_density)
-    print(f"[main_nerf] checkpoint {ckpt} (step {state.get('global_step', '?')})")
+    # a full checkpoint of an EMA run: the averaged weights are what is rendered, as the reference's
+    # trainer does after load_checkpoint (nerf/utils.py:1261-1262, 881-883); the mesh is the model's own
+    source = None
+    if isinstance(state.get("ema"), dict):
+        source = [t.to(dev, torch.float32).contiguous() for t in state["ema"]["shadow_params"]]
+    print(f"[main_nerf] checkpoint {ckpt} (step {state.get('global_step', '?')}"
+          + (", EMA weights" if source is not None else "") + ")")
     result = {"checkpoint": ckpt}
-    result.update(_write_test_frames(opt, model, None, dev, data_args))
+    result.update(_write_test_frames(opt, model, None, dev, data_args, source))
     if opt.save_mesh:
         path = os.path.join(opt.workspace, "meshes", "ngp.ply")
         nv, nt = mesh.save_mesh(model, path, resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)
@@ -174,7 +207,7 @@ def main(argv=None):
 
     import torch
 
-    from nerf.eval import depth_error, psnr
+    from nerf.eval import Validator, depth_error, psnr
     from nerf.fused import FusedTrainer
     from nerf.fused_render import FusedRenderer
     from nerf.network_ff import NeRFNetwork
@@ -187,6 +220,15 @@ def main(argv=None):
                      depth_scale=opt.depth_scale)
     if opt.test:
         return _test(opt, dev, bound, data_args)
+    state = None
+    if opt.resume:
+        ckpt = _ckpt_path(opt)
+        if not os.path.exists(ckpt):
+            sys.exit(f"[main_nerf] --resume: no checkpoint at {ckpt} (train first, or name one with --ckpt)")
+        state = torch.load(ckpt, map_location="cpu", weights_only=False)
+        if "optimizer" not in state:
+            sys.exit(f"[main_nerf] --resume: {ckpt} holds no optimizer state (a best checkpoint): it can be "
+                     "rendered with --test, not trained on")
     try:
         train = NeRFDataset(opt.path, dev, type="train", num_rays=opt.num_rays, error_map=opt.error_map,
                             error_map_res=opt.error_map_res, **data_args)
@@ -200,9 +242,25 @@ def main(argv=None):
     try:
         ft = FusedTrainer(model, train, M=M, lr=opt.lr, iters=opt.iters, max_steps=opt.max_steps,
                           dt_gamma=opt.dt_gamma, seed=opt.seed, depth_loss_weight=opt.depth_loss_weight,
-                          color_loss_weight=opt.color_loss_weight)
+                          color_loss_weight=opt.color_loss_weight, ema_decay=opt.ema_decay)
     except ValueError as e:  # e.g. a depth weight on a scene without depth maps
         sys.exit(f"[main_nerf] {e}")
+    ema = opt.ema_decay is not None
+    # an epoch is one step per training view (the reference's len(train_loader), batch size 1); the position
+    # in it follows from the step count alone, so a checkpoint of a run that counted no epochs resumes right
+    epoch_len = int(train.poses.shape[0])
+    stats, done = None, 0
+    if state is not None:
+        ft.load_checkpoint(state)
+        stats, done = state["stats"], int(state["global_step"])
+        print(f"[main_nerf] resumed {ckpt} at step {done} (epoch {done // epoch_len}"
+              + (f", {ft.num_updates} EMA updates" if ema else "") + ")")
+        if ema and not isinstance(state.get("ema"), dict):
+            # the shadow built with the trainer averages the initial weights: start it at the loaded ones
+            ft.ema_reset()
+            print(f"[main_nerf] {ckpt} carries no EMA: the average starts from its weights")
+    start = done
+    epoch, in_epoch = divmod(done, epoch_len)
     print(f"[main_nerf] {train.images.shape[0]} images {train.H}x{train.W}x{train.images.shape[3]} "
           f"({train.images.numel() / 2 ** 20:.0f} MiB uint8), {opt.num_rays} rays/step, sample budget {M}"
           + (f", error map {opt.error_map_res}x{opt.error_map_res}" if opt.error_map else "")
@@ -213,20 +271,78 @@ def main(argv=None):
     every = max(1, int(opt.update_extra_interval))
     log_every = max(every, opt.iters // 20 // every * every)
     over = torch.zeros((), dtype=torch.int64, device=dev)  # recorded steps whose samples passed the budget
-    checked, done, captured = 0, 0, False
-    t0 = time.perf_counter()
-    while done < opt.iters:
-        # the reference's cadence (utils.py:580-582): an update at every interval's first step
-        ft.update_density()
-        k = min(every, opt.iters - done)
+    checked, captured = 0, False
+    # epochs matter only to the EMA and the periodic validation: without both the loop below issues
+    # today's calls
+    use_epochs = ema or opt.eval_interval > 0
+    split = _eval_split(opt.path)
+    val, validator, ckpt_dir = None, None, os.path.join(opt.workspace, "checkpoints")
+    if stats is None:
+        stats = {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None}
+    valid_psnr, best_ckpt = [], None
+    if opt.eval_interval > 0:
+        val = train if split == "train" else NeRFDataset(opt.path, dev, type=split, num_rays=opt.num_rays,
+                                                         **data_args)
+        validator = Validator(model, val, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma)
+
+    def advance(k):
+        nonlocal captured
         if captured:
             ft.run(k)
         else:
             for _ in range(k):  # the first interval eagerly, then the graphs
                 ft.step()
-            if k == every and done + k < opt.iters:
-                ft.capture(warmup=0, multi=max(every - 1, 1))
-                captured = True
+
+    def end_epoch():
+        """The reference's end of train_one_epoch / evaluate_one_epoch / save_checkpoint(best=True)
+        (nerf/utils.py:1051-1052, 731-733, 1213-1233)."""
+        nonlocal best_ckpt
+        if ema:
+            ft.ema_update()
+        if validator is None or epoch % opt.eval_interval:
+            return
+        ft.flush()
+        torch.cuda.synchronize()
+        tv = time.perf_counter()
+        res = validator.run(source=ft.ema_params() if ema else None)
+        tv = time.perf_counter() - tv
+        print(f"[main_nerf] epoch {epoch} validation PSNR {res['mean_psnr']:.4f} over {len(res['views'])} {split} "
+              f"images ({tv:.3f} s)")
+        stats["valid_loss"].append(res["mean_mse"])
+        valid_psnr.append(res["mean_psnr"])
+        if stats["best_result"] is None or res["mean_psnr"] > stats["best_result"]:
+            stats["best_result"] = res["mean_psnr"]
+            best = ft.checkpoint(full=False, epoch=epoch, stats=stats)
+            best["model"] = dict(best["model"])
+            if ema:  # the averaged weights under the parameters' names
+                names = {id(p): n for n, p in model.named_parameters()}
+                for p, shadow in zip(ft.params, ft.ema_params()):
+                    best["model"][names[id(p)]] = shadow.detach().cpu()  # (loads without a GPU)
+            best["model"].pop("density_grid", None)  # (not trained on again, as the reference's)
+            os.makedirs(ckpt_dir, exist_ok=True)
+            best_ckpt = os.path.join(ckpt_dir, "ngp_best.pth")
+            torch.save(best, best_ckpt)
+
+    t0 = time.perf_counter()
+    while done < opt.iters:
+        # the reference's cadence (utils.py:580-582): an update at every interval's first step
+        if done % every == 0:
+            ft.update_density()
+        k = min(every - done % every, opt.iters - done)
+        if not use_epochs:
+            advance(k)
+        else:  # an interval that contains an epoch boundary runs in two parts
+            left = k
+            while left:
+                part = min(left, epoch_len - in_epoch)
+                advance(part)
+                left, in_epoch = left - part, in_epoch + part
+                if in_epoch == epoch_len:
+                    epoch, in_epoch = epoch + 1, 0
+                    end_epoch()
+        if not captured and k == every and done + k < opt.iters:
+            ft.capture(warmup=0, multi=max(every - 1, 1))
+            captured = True
         done += k
         n = min(k, 16)
         over += ft.over_budget(n)
@@ -240,15 +356,19 @@ def main(argv=None):
     torch.cuda.synchronize()
     secs = time.perf_counter() - t0
     errors = ft.device_errors()
-    print(f"[main_nerf] trained {opt.iters} steps in {secs:.1f} s; {int(over.item())} of {checked} recorded steps "
-          f"passed the sample budget of {M} rows (their last rays were dropped); device errors {errors}")
+    print(f"[main_nerf] trained {opt.iters - start} steps in {secs:.1f} s; {int(over.item())} of {checked} recorded "
+          f"steps passed the sample budget of {M} rows (their last rays were dropped); device errors {errors}")
 
     # evaluation: the reference's eval_step over the val (or test) split
-    split = _eval_split(opt.path)
-    val = train if split == "train" else NeRFDataset(opt.path, dev, type=split, num_rays=opt.num_rays, **data_args)
+    # (with --ema_decay from the averaged weights, as every PSNR the reference reports is)
+    if val is None:
+        val = train if split == "train" else NeRFDataset(opt.path, dev, type=split, num_rays=opt.num_rays,
+                                                         **data_args)
     model.eval()
-    renderer = FusedRenderer(model, val.H * val.W, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma)
-    renderer.load_weights()
+    source = ft.ema_params() if ema else None
+    renderer = validator.frames.renderer if validator is not None else \
+        FusedRenderer(model, val.H * val.W, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma)
+    renderer.load_weights(source)
     scores = [psnr(model, val, i, dt_gamma=opt.dt_gamma, renderer=renderer) for i in range(val.poses.shape[0])]
     finite = [s for s in scores if math.isfinite(s)]
     mean_psnr = sum(finite) / len(finite) if finite else float("inf")
@@ -263,15 +383,15 @@ def main(argv=None):
         print(f"[main_nerf] depth error {mean_depth:.6f} over {val.poses.shape[0]} {split} images")
     model.train()
 
-    ckpt_dir = os.path.join(opt.workspace, "checkpoints")
     os.makedirs(ckpt_dir, exist_ok=True)
     ckpt = os.path.join(ckpt_dir, "ngp.pth")
-    state = ft.checkpoint()
+    state = ft.checkpoint(epoch=epoch if use_epochs else 0, stats=stats)
     state["stats"]["results"].append(mean_psnr)
     torch.save(state, ckpt)
     print(f"[main_nerf] checkpoint {ckpt}")
     result = {"psnr": mean_psnr, "loss": ft.last_loss, "over_budget": int(over.item()), "checkpoint": ckpt,
-              "seconds": secs, "depth_error": mean_depth}
+              "seconds": secs, "depth_error": mean_depth, "start_step": start, "epoch": epoch,
+              "valid_psnr": valid_psnr, "best_checkpoint": best_ckpt}
     if opt.save_mesh:
         ft.workspace = opt.workspace
         path, nv, nt = ft.save_mesh(resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)
@@ -279,7 +399,7 @@ def main(argv=None):
               f"(resolution {opt.mesh_resolution}, threshold {opt.mesh_threshold:g})")
         result.update(mesh=path, mesh_vertices=nv, mesh_triangles=nt)
     if opt.write_frames:
-        result.update(_write_test_frames(opt, model, train, dev, data_args))
+        result.update(_write_test_frames(opt, model, train, dev, data_args, source))
     return result
 
 

@@ -1,10 +1,18 @@
 """Evaluation of a trained model against a dataset's images: the reference's
 eval_step (nerf/utils.py:636-642) on the device-driven test render; and
-against its depth maps: the supervised depth term over a whole view."""
+against its depth maps: the supervised depth term over a whole view.
+Validator is the same comparison kept on the device:
+the frame renderer's rays and loop, then the squared error against the image
+stack in one launch per view and one read-back per pass."""
+import ctypes
 import math
 
+import numpy as np
 import torch
 
+import _ngp_native as nat
+
+from .frames import FrameRenderer
 from .fused_render import FusedRenderer
 from .utils import get_rays
 
@@ -69,3 +77,82 @@ def depth_error(model, dataset, index, dt_gamma=0.0, max_steps=1024, chunk=4096)
     mask = (model.min_near <= gt) & (gt <= model.bound)
     err = torch.abs(gt - torch.cat(pred, 1))[mask]
     return float(err.mean().item()) if err.numel() else float("nan")
+
+
+class Validator:
+    """The reference's evaluate_one_epoch (nerf/utils.py:1075-1173) over a
+    dataset's views without leaving the device: a FrameRenderer over the
+    dataset's poses and a [n_views] double buffer. Per view: ngp_frame_begin
+    (the pose's rays), the render loop, ngp_frame_sse (the blend on white and
+    the squared error against dataset.images[view], summed in double). The
+    buffer is read back once per pass; the only other host synchronisation is
+    the render loop's own 16-byte state read per graph replay."""
+
+    def __init__(self, model, dataset, max_steps=1024, dt_gamma=0.0):
+        images = getattr(dataset, "images", None)
+        if images is None:
+            raise ValueError("Validator: the dataset has no images (dataset.images)")
+        self.model, self.data = model, dataset
+        self.H, self.W = int(dataset.H), int(dataset.W)
+        self.n = int(dataset.poses.shape[0])
+        self.frames = FrameRenderer(model, self.H, self.W, dataset.intrinsics, max_steps=max_steps,
+                                    dt_gamma=dt_gamma, bg_color=1.0)
+        dev = self.frames.dev
+        if images.dim() != 4 or tuple(images.shape[:3]) != (self.n, self.H, self.W) or images.shape[3] not in (3, 4):
+            raise ValueError(f"Validator: dataset.images must be [n_poses, H, W, 3 or 4] = "
+                             f"[{self.n}, {self.H}, {self.W}, 3 | 4], got {list(images.shape)}")
+        if images.dtype not in (torch.uint8, torch.float32) or not images.is_contiguous() or images.device != dev:
+            raise ValueError(f"Validator: dataset.images must be contiguous uint8 or float32 on {dev}, got "
+                             f"{images.dtype} on {images.device}")
+        self._images = images  # (kept alive with its pointer)
+        self._src = nat.ImageSource()
+        self._src.pixels, self._src.channels = nat.ptr(images), int(images.shape[3])
+        self._src.dtype = nat.DTYPE_U8 if images.dtype == torch.uint8 else nat.DTYPE_CODE[torch.float32]
+        self.frames.set_poses(dataset.poses)
+        self.sse = torch.zeros(self.n, dtype=torch.float64, device=dev)
+
+    def sse_view(self, i):
+        """View i rendered with the loaded weights, its squared error into
+        self.sse[i] (no read-back)."""
+        fr = self.frames
+        r, P = fr.renderer, nat.ptr
+        fr.begin(i)
+        r.run_loop()
+        bg_color = fr.bg_color
+        if r._bg:  # as FrameRenderer.render: the model's background blended in place, then nothing to add
+            r.background(blend=True)
+            bg_color = 0.0
+        nat.check(nat.lib().ngp_frame_sse(self.H, self.W, P(r.image), P(r.weights_sum), bg_color,
+                                          ctypes.byref(self._src), i, P(self.sse), r._stream()), "frame_sse")
+
+    @torch.no_grad()
+    def run(self, source=None, views=None):
+        """Every view (or `views`, a list of indices) of the dataset rendered
+        in eval mode from `source` (FusedRenderer.load_weights: None, the
+        model's own weights; FusedTrainer.ema_params(), the averaged ones) ->
+        dict(views, mse, psnr: float64 arrays by position in views; mean_mse;
+        mean_psnr, over the views with a finite PSNR as main_nerf's final
+        evaluation takes it). mse = sse / (3 H W), psnr = -10 log10(mse)."""
+        views = list(range(self.n)) if views is None else [int(v) for v in views]
+        for v in views:
+            if not 0 <= v < self.n:
+                raise IndexError(f"Validator: view {v} of {self.n}")
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            self.frames.load_weights(source)
+            if self.frames.renderer.graph is None:
+                self.frames.capture()
+            for v in views:
+                self.sse_view(v)
+        finally:
+            self.model.train(was_training)
+        sse = self.sse.cpu().numpy()[views]  # the pass's one read-back
+        mse = sse / float(3 * self.H * self.W)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            psnr_ = np.where(mse > 0, -10.0 * np.log10(mse), np.inf)
+        psnr_ = np.where(np.isfinite(mse), psnr_, np.nan)
+        finite = psnr_[np.isfinite(psnr_)]
+        return {"views": views, "mse": mse, "psnr": psnr_,
+                "mean_mse": float(mse.mean()) if len(views) else float("nan"),
+                "mean_psnr": float(finite.mean()) if finite.size else float("inf")}

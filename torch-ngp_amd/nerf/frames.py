@@ -52,8 +52,10 @@ class FrameRenderer:
         self.poses = None
         self._host = None  # frames(): two pinned (rgb, depth) pairs and their events
 
-    def load_weights(self):
-        self.renderer.load_weights()
+    def load_weights(self, source=None):
+        """source: the weights to render instead of the model's own
+        (FusedRenderer.load_weights), e.g. FusedTrainer.ema_params()."""
+        self.renderer.load_weights(source)
 
     def capture(self):
         self.renderer.capture()

@@ -130,7 +130,7 @@ class FusedTrainer:
     def __init__(self, model, dataset, M, lr=1e-2, iters=30000, max_steps=1024, T_thresh=1e-4,
                  dt_gamma=0.0, seed=0, betas=(0.9, 0.99), eps=1e-15, init_scale=65536.0,
                  growth_interval=2000, distributed=False, grid_timing=False, options=None,
-                 depth_loss_weight=0.0, color_loss_weight=1.0, error_map=None):
+                 depth_loss_weight=0.0, color_loss_weight=1.0, error_map=None, ema_decay=None):
         """distributed: ray-sharded data parallelism over the initialised
         torch.distributed group: each rank draws its own rays; the flat fp16
         gradient is averaged with one RCCL reduce-scatter, each rank's Adam
@@ -156,7 +156,12 @@ class FusedTrainer:
         launch that draws), and each step folds its rays' colour errors back
         into those cells (ngp_error_map_update, one launch after the
         composite). None: on exactly when the dataset has a map; False: the
-        uniform draw, launch for launch, whatever the dataset has. World 1 only."""
+        uniform draw, launch for launch, whatever the dataset has. World 1 only.
+        ema_decay: the reference's exponential moving average of the parameters
+        (torch_ema through Trainer(ema_decay=0.95)): a
+        float32 shadow of flat_param, updated by `ema_update()` (the caller's,
+        once per epoch), read through `ema_params()`, saved and restored with
+        the checkpoint. None: no shadow and no launch anywhere. World 1 only."""
         opts = dict(DEFAULT_OPTIONS)
         for k, v in (options or {}).items():
             if k not in opts:
@@ -185,6 +190,13 @@ class FusedTrainer:
         if self.depth_loss_weight > 0 and depths is None:
             raise ValueError("FusedTrainer: depth_loss_weight > 0 needs a dataset with depth maps (dataset.depths: "
                              "a dep_path per frame, nerf.provider.NeRFDataset); this one has none")
+        if ema_decay is not None:
+            if distributed:
+                raise ValueError("FusedTrainer: ema_decay is single-process only: each rank of a data-parallel "
+                                 "run holds the masters of its shard between flushes (distributed=True)")
+            if not 0.0 <= float(ema_decay) <= 1.0:
+                raise ValueError(f"FusedTrainer: ema_decay must be in [0, 1], got {ema_decay}")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.density_seed = int(seed)  # the density-grid draws are the same on every rank
         # dp: the data-parallel (ZeRO-1) step with its collectives, also at
         # world size 1 (a one-rank group runs the same RCCL calls);
@@ -267,6 +279,10 @@ class FusedTrainer:
                 p.data = view
                 self.flat_half[int(a):int(a) + p.numel()].copy_(view.reshape(-1))
         self._starts = [int(a) for a in starts[:-1]]
+        # EMA shadow: the same flat layout, so one launch updates every tensor (the alignment
+        # padding is zero in both and stays zero: 0 - omd * (0 - 0))
+        self.ema_shadow = self.flat_param.clone() if self.ema_decay is not None else None
+        self.num_updates = 0  # torch_ema's counter: the decay's warm-up
         self.grads = [self.flat_grad[int(a):int(a) + n].view(p.shape)
                       for a, n, p in zip(starts[:-1], sizes, self.params)]
         self.w_half = [self.flat_half[int(a):int(a) + n].view(p.shape)
@@ -1448,6 +1464,38 @@ class FusedTrainer:
         if self._xchg is not None and self._xchg.check():
             self._recapture()
 
+    def ema_update(self):
+        """ExponentialMovingAverage.update() (torch_ema; the reference calls it
+        once per epoch, nerf/utils.py:1051-1052): the pending optimizer step is
+        applied, then shadow -= (1 - decay) * (shadow - param) over the flat
+        buffer in one launch, decay = min(ema_decay, (1 + n) / (10 + n)) with n
+        the updates made, this one included."""
+        if self.ema_shadow is None:
+            raise RuntimeError("FusedTrainer.ema_update: the trainer was built without ema_decay")
+        self.flush()
+        self.num_updates += 1
+        decay = min(self.ema_decay, (1 + self.num_updates) / (10 + self.num_updates))
+        nat.check(nat.lib().ngp_ema_update(nat.ptr(self.ema_shadow), nat.ptr(self.flat_param), self.total,
+                                           float(np.float32(1.0 - decay)), nat.stream_of(self.flat_param)),
+                  "ema_update")
+
+    def ema_reset(self):
+        """The average starts again from the current parameters (after loading
+        weights that came without an EMA): shadow = flat_param, no updates made."""
+        if self.ema_shadow is None:
+            raise RuntimeError("FusedTrainer.ema_reset: the trainer was built without ema_decay")
+        self.flush()
+        self.ema_shadow.copy_(self.flat_param)
+        self.num_updates = 0
+
+    def ema_params(self):
+        """Views of the shadow, one per tensor of self.params in that order and
+        with its shape: what FusedRenderer / FrameRenderer.load_weights and
+        nerf.eval.Validator.run take as `source`."""
+        if self.ema_shadow is None:
+            raise RuntimeError("FusedTrainer.ema_params: the trainer was built without ema_decay")
+        return [self.ema_shadow[a:a + p.numel()].view(p.shape) for a, p in zip(self._starts, self.params)]
+
     def save_mesh(self, path=None, resolution=256, threshold=10):
         """Trainer.save_mesh (nerf/utils.py:688-708): the pending update is
         applied first, then nerf.mesh.save_mesh writes the density field's mesh
@@ -1762,7 +1810,10 @@ class FusedTrainer:
         state_dicts in torch's own formats (torch.optim.Adam over
         model.get_params(lr), LambdaLR, GradScaler load them), so checkpoints
         move between the reference's trainer and this one. `fused` carries the
-        sampler's draw counter (not part of the reference format)."""
+        sampler's draw counter (not part of the reference format). With
+        ema_decay and full, `ema` is torch_ema's state_dict (utils.py:1195):
+        decay, num_updates, shadow_params (a list of tensors in
+        model.parameters() order, which is self.params'), collected_params None."""
         self.flush()
         si = self.state.view(torch.int32).cpu()
         scale = float(self.state.view(torch.float32)[self._S_SCALE].item())
@@ -1801,6 +1852,10 @@ class FusedTrainer:
                                      "lr_lambdas": [None] * ng}
             state["scaler"] = {"scale": scale, "growth_factor": 2.0, "backoff_factor": 0.5,
                                "growth_interval": self.growth_interval, "_growth_tracker": int(si[self._S_GROWTH])}
+            if self.ema_shadow is not None:
+                state["ema"] = {"decay": self.ema_decay, "num_updates": self.num_updates,
+                                "shadow_params": [t.clone() for t in self.ema_params()],
+                                "collected_params": None}
         return state
 
     def load_checkpoint(self, state, model_only=False):
@@ -1858,3 +1913,12 @@ class FusedTrainer:
         if "scaler" in state:
             self.state.view(torch.float32)[self._S_SCALE] = float(state["scaler"]["scale"])
             si[self._S_GROWTH] = int(state["scaler"]["_growth_tracker"])
+        if self.ema_shadow is not None and state.get("ema") is not None:
+            ema = state["ema"]
+            shadows = ema["shadow_params"]
+            if len(shadows) != len(self.params):
+                raise ValueError(f"FusedTrainer.load_checkpoint: the checkpoint's EMA holds {len(shadows)} tensors, "
+                                 f"this trainer's model has {len(self.params)}")
+            for dst, src in zip(self.ema_params(), shadows):
+                dst.copy_(src.to(self.dev, torch.float32).reshape(dst.shape))
+            self.num_updates = int(ema["num_updates"] or 0)  # (torch_ema: None when built without warm-up)

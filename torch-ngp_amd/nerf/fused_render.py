@@ -75,23 +75,54 @@ class FusedRenderer:
             self.w_half_bg = z(model.bg_net.weights.numel(), dtype=h)
             self._bg_grid = (eb.num_levels, eb.level_dim, float(np.log2(eb.per_level_scale)), eb.base_resolution)
         self.graph = None
+        self._graph_table = None  # the table address the graph was captured with
+        self._source = None  # load_weights(source): the tables the loop reads instead of the model's
         self.iterations = 0  # device iterations of the last render (graph replays x K)
 
     def _stream(self):
         return nat.stream_of(self.rays_o)
 
-    def load_weights(self):
+    def load_weights(self, source=None):
         """fp16 copies of the MLP weights (autocast's casts) and their MFMA
         fragment images; the table is read in fp32 and rounded to half on load,
-        the value autocast's cast gives. Call after the weights changed."""
+        the value autocast's cast gives. Call after the weights changed.
+        source: the weights to render, one tensor per parameter in
+        FusedTrainer.params order (hash table, sigma MLP, colour MLP and, of a
+        model with a background, its grid and MLP), e.g. FusedTrainer's
+        ema_params(); None: the model's own. The MLP images are packed from it
+        and the loop reads its tables in place; nothing of the model is
+        written. A captured graph holds the table's address, so it is captured
+        again when that changes."""
+        m = self.model
+        own = [m.encoder.embeddings, m.sigma_net.weights, m.color_net.weights]
+        if self._bg:
+            own += [m.encoder_bg.embeddings, m.bg_net.weights]
+        if source is not None:
+            source = [t.detach() for t in source]
+            if len(source) != len(own):
+                raise ValueError(f"load_weights: source must hold {len(own)} tensors (FusedTrainer.params order), "
+                                 f"got {len(source)}")
+            for k, (t, p) in enumerate(zip(source, own)):
+                if t.numel() != p.numel() or t.dtype != p.dtype or t.device != p.device or not t.is_contiguous():
+                    raise ValueError(f"load_weights: source[{k}] must be a contiguous {p.dtype} tensor of "
+                                     f"{p.numel()} values on {p.device}")
+        self._source = source
+        source = own if source is None else source
         with torch.no_grad():
-            self.w_half[0].copy_(self.model.sigma_net.weights.detach().reshape(-1))
-            self.w_half[1].copy_(self.model.color_net.weights.detach().reshape(-1))
+            self.w_half[0].copy_(source[1].detach().reshape(-1))
+            self.w_half[1].copy_(source[2].detach().reshape(-1))
             if self._bg:
-                self.w_half_bg.copy_(self.model.bg_net.weights.detach().reshape(-1))
+                self.w_half_bg.copy_(source[4].detach().reshape(-1))
         pk = self._pk
         nat.check(nat.lib().ngp_ffmlp_pack(2, pk["w"], pk["ins"], pk["hid"], pk["nl"], pk["img"], self._stream()),
                   "ffmlp_pack")
+        if self.graph is not None and self._graph_table != self._table().data_ptr():
+            self.capture()
+
+    def _table(self, bg=False):
+        if self._source is not None:
+            return self._source[3 if bg else 0]
+        return (self.model.encoder_bg if bg else self.model.encoder).embeddings
 
     def _iteration(self, i):
         lib, P, s, m = nat.lib(), nat.ptr, self._stream(), self.model
@@ -102,7 +133,7 @@ class FusedRenderer:
                                        float(m.bound), self.dt_gamma, self.max_steps, m.cascade, m.grid_size,
                                        P(m.density_bitfield), P(self.fars), P(self.xyzs), P(self.dirs),
                                        P(self.deltas), P(self.noises), s), "render_march")
-        nat.check(lib.ngp_grid_encode_forward_fused(P(self.xyzs), float(m.bound), P(e.embeddings), _F32,
+        nat.check(lib.ngp_grid_encode_forward_fused(P(self.xyzs), float(m.bound), P(self._table()), _F32,
                                                     P(e.offsets), P(self.enc_out), N, cnt, e.input_dim, e.level_dim,
                                                     e.num_levels, self.S, e.base_resolution, e.gridtype_id,
                                                     int(e.align_corners), e.interp_id, 0, s), "grid_encode_fused")
@@ -136,6 +167,7 @@ class FusedRenderer:
         with torch.cuda.graph(g):
             self._iterations()
         self.graph = g
+        self._graph_table = self._table().data_ptr()
 
     def run_loop(self):
         """The loop on initialised rays and state (ngp_render_init, or
@@ -161,7 +193,7 @@ class FusedRenderer:
         m, P = self.model, nat.ptr
         eb, bn = m.encoder_bg, m.bg_net
         nat.check(nat.lib().ngp_background_forward(
-            P(self.rays_o), P(self.rays_d), float(m.bg_radius), self.N, P(eb.embeddings), _F32, P(eb.offsets),
+            P(self.rays_o), P(self.rays_d), float(m.bg_radius), self.N, P(self._table(bg=True)), _F32, P(eb.offsets),
             *self._bg_grid, P(self.w_half_bg), bn.input_dim, bn.hidden_dim, bn.num_layers, P(self.bg), None, None,
             None, P(self.image) if blend else None, P(self.weights_sum) if blend else None, self._stream()),
             "background_forward")
