@@ -205,7 +205,8 @@ k_grid_fwd(const float* __restrict__ inputs, const E* __restrict__ grid,
         F v[C];
         load_entry_as<T, E, C>(g + (size_t)e * C, v);
 #pragma unroll
-        for (uint32_t c = 0; c < C; ++c) res[c] = A::mac(res[c], (F)w, v[c]);
+        // (mac_opaque, ngp_common.h: the product is rounded to float, then to half, in every instantiation)
+        for (uint32_t c = 0; c < C; ++c) res[c] = A::mac_opaque(res[c], (F)w, v[c]);
     }
     store_entry<T, C>(out, res);
 
@@ -418,7 +419,9 @@ NGP_DEV void grid_fwd_pair_block(uint32_t blk, const float* __restrict__ inputs,
             for (uint32_t c = 0; c < C; ++c) {
                 const F other = (F)ngp_dpp::pair_swap((float)mine[q][rest][c]);  // DPP, every lane active
                 const F v = ((idx & 1u) == xbit) ? mine[q][rest][c] : other;
-                res[c] = A::mac(res[c], (F)w, v);
+                // (Acc::mac_opaque, ngp_common.h: the D 3, C 2 kernels keep their packed code)
+                if constexpr (D == 3 && C == 2) res[c] = A::mac(res[c], (F)w, v);
+                else res[c] = A::mac_opaque(res[c], (F)w, v);
             }
         }
         if (live && xbit == 0) {
@@ -770,7 +773,7 @@ constexpr uint32_t kMergeMaxRes = NGP_MERGE_MAX_RES;
 struct BinPlan {
     uint32_t nlev;                   // levels [0, nlev) are binned
     uint32_t total_bins;
-    uint32_t merge_mask;             // levels whose equal-corner runs are merged in-wave
+    uint64_t merge_mask;             // levels whose equal-corner runs are merged in-wave (one bit per level, kMaxLevels <= 64)
     uint32_t nbins[kMaxLevels];
     uint32_t bin0[kMaxLevels];       // first global bin of the level
     uint32_t cap[kMaxLevels];        // item capacity per bin
@@ -970,7 +973,7 @@ NGP_DEV void bin_block(const ngp_half* __restrict__ grad, const float* __restric
     if (chunk != by) __syncthreads();  // the last block's write-out has read the LDS
     [[maybe_unused]] const uint32_t stamp_id = level * gy + chunk;
     const uint32_t nb = bp.nbins[level];
-    const bool merge = (bp.merge_mask >> level) & 1u;
+    const bool merge = (bp.merge_mask >> level) & 1ull;
     const int lane = (int)(threadIdx.x & 63);
     for (uint32_t j = threadIdx.x; j < nb; j += kBinPts) cnt[j] = 0;
     lds_barrier();
@@ -2155,7 +2158,7 @@ static BinPlan make_bin_plan(const int32_t* offsets_host, uint32_t L, uint32_t D
         bp.bin0[l] = bins;
         bp.cap[l] = (uint32_t)std::max<uint64_t>(cap, 1);
         bp.item0[l] = (uint32_t)slots;
-        if (lv.res[l] <= kMergeMaxRes) bp.merge_mask |= 1u << l;  // cells span several ray steps
+        if (lv.res[l] <= kMergeMaxRes) bp.merge_mask |= 1ull << l;  // cells span several ray steps
         bp.mslot0[l] = bp.cap[l] > kSegItems ? bp.nmslots : kNoSlot;
         if (bp.cap[l] > kSegItems) bp.nmslots += nb;
         bins += nb;

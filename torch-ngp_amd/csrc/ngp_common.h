@@ -54,6 +54,7 @@ template <> struct Acc<float> {
     NGP_DEV static F load(const float* p) { return *p; }
     NGP_DEV static S zero() { return 0.0f; }
     NGP_DEV static S mac(S res, F a, F b) { return fmaf(a, b, res); }  // nvcc contracts res += a*b
+    NGP_DEV static S mac_opaque(S res, F a, F b) { return mac(res, a, b); }
     NGP_DEV static F to_f(S v) { return v; }
 };
 template <> struct Acc<ngp_half> {
@@ -65,6 +66,22 @@ template <> struct Acc<ngp_half> {
         ngp_half prod = (ngp_half)(a * b);
         return (ngp_half)((float)res + (float)prod);
     }
+    // mac with the product rounded to float and THEN to half whatever the
+    // compiler selects. Left to it, (half)(a * b) becomes v_fma_mixlo_f16 in
+    // some instantiations (the pair forward at D 4 and 5, k_grid_fwd), which
+    // rounds the exact product ONCE: about one product in 2^13 then lands on
+    // the other side of a half rounding boundary and the encoding differs from
+    // the reference's by an ulp or two. The empty asm keeps the float product
+    // opaque and emits nothing, but it also keeps the compiler from packing
+    // the multiplies and conversions in pairs, so the D 3, C 2 forward kernels
+    // (the train step's; v_pk_mul_f32 + v_cvt_pk_f16_f32, bit-exact at scale
+    // in tests/test_gpu_grid_fused.py) stay on mac.
+    NGP_DEV static S mac_opaque(S res, F a, F b) {
+        float p = a * b;
+        asm("" : "+v"(p));
+        ngp_half prod = (ngp_half)p;
+        return (ngp_half)((float)res + (float)prod);
+    }
     NGP_DEV static F to_f(S v) { return (float)v; }
 };
 template <> struct Acc<double> {
@@ -73,5 +90,6 @@ template <> struct Acc<double> {
     NGP_DEV static F load(const double* p) { return *p; }
     NGP_DEV static S zero() { return 0.0; }
     NGP_DEV static S mac(S res, F a, F b) { return fma(a, b, res); }
+    NGP_DEV static S mac_opaque(S res, F a, F b) { return mac(res, a, b); }
     NGP_DEV static F to_f(S v) { return v; }
 };
