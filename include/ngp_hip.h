@@ -206,6 +206,18 @@ int ngp_composite_rays_train_backward(const float* grad_weights_sum, const float
                                       const float* weights_sum, const float* depth,
                                       const float* image, uint32_t M, uint32_t N, float T_thresh,
                                       float* grad_sigmas, float* grad_rgbs, void* stream);
+/* The distortion regulariser (the reference's loss.py EffDistLoss) on the
+ * training composite's weights, serial per ray with the composite's
+ * T *= 1 - alpha recurrence and stop rule:
+ *   dist[ray index] = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i deltas[i][0] w_i^2
+ * (m the running sum of deltas[.][1]; 0 for a ray without samples or dropped
+ * for overflowing M). The backward writes grad_dist[ray] * d dist / d sigma for
+ * the samples up to the stop; the caller zeroes grad_sigmas [M]. */
+int ngp_distortion_rays_train_forward(const float* sigmas, const float* deltas, const int32_t* rays,
+                                      uint32_t M, uint32_t N, float T_thresh, float* dist, void* stream);
+int ngp_distortion_rays_train_backward(const float* grad_dist, const float* sigmas, const float* deltas,
+                                       const int32_t* rays, const float* dist, uint32_t M, uint32_t N,
+                                       float T_thresh, float* grad_sigmas, void* stream);
 /* raymarching.h:17, raymarching.cu:817-825 */
 int ngp_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive,
                    const float* rays_t, const float* rays_o, const float* rays_d, float bound,
@@ -833,6 +845,38 @@ int ngp_nerf_composite_loss_depth_lists(const float* sigma, const void* color_ou
                                         const float* bg, void* state, void* grad_color_out, void* grad_h_sigma,
                                         float* out_image, float* out_ws, float* loss_ray,
                                         const ngp_depth_loss_job* job, void* stream);
+/* The distortion regulariser of mip-NeRF 360 in its O(n) form (the reference's
+ * loss.py EffDistLoss), on the composite's own weights: per ray, with
+ * delta_i = deltas[i][0], m_i the composite's t (the running sum of
+ * deltas[.][1]) and w_i the composite's weight (0 past the early stop),
+ *   dist = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i delta_i w_i^2
+ * in ngp units; 0 for a ray without samples or dropped for overflowing M.
+ *   loss_ray[n] = the depth entry's value + weight * dist
+ * and scale * weight / N * d dist / d sigma is added to the density gradient
+ * before its one rounding to half. weight 0: dist is still computed and
+ * written, the loss, the gradients and the live lists are the depth entry's
+ * bit for bit. */
+typedef struct ngp_dist_loss_job {
+    float weight;          /* >= 0 */
+    float* loss_dist_ray;  /* nullable f32 [N], ray n's unweighted dist (by list position, as loss_ray) */
+} ngp_dist_loss_job;
+/* ngp_nerf_composite_loss_depth plus the distortion term. job is required and
+ * keeps its meaning (color_weight 1, depth_weight 0 and a null gt_depth give
+ * the colour-only loss; it carries the live lists). A null dist, or a negative
+ * or non-finite weight: NGP_ERR_ARG before any device work. */
+int ngp_nerf_composite_loss_dist(const float* sigma, const void* color_out, const void* h_sigma,
+                                 const float* deltas, const int32_t* rays, uint32_t M, uint32_t N, float T_thresh,
+                                 float density_scale, const float* gt, uint32_t gt_channels, const float* bg,
+                                 void* state, void* grad_color_out, void* grad_h_sigma, float* out_image,
+                                 float* out_ws, float* loss_ray, const ngp_depth_loss_job* job,
+                                 const ngp_dist_loss_job* dist, void* stream);
+/* .._dist as ngp_nerf_composite_loss_depth_lists. One launch. */
+int ngp_nerf_composite_loss_dist_lists(const float* sigma, const void* color_out, const void* h_sigma,
+                                       const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                       float T_thresh, float density_scale, const float* gt, uint32_t gt_channels,
+                                       const float* bg, void* state, void* grad_color_out, void* grad_h_sigma,
+                                       float* out_image, float* out_ws, float* loss_ray,
+                                       const ngp_depth_loss_job* job, const ngp_dist_loss_job* dist, void* stream);
 /* scaler_enabled of the optimizer entries: GradScaler off; on, with its inf
  * check as a sweep over the grads; on, with the check already made by the
  * kernels that wrote the grads into the state's flag (ngp_fused_inf_flag). */

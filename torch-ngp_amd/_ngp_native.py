@@ -63,6 +63,8 @@ SIGNATURES = {
                                          c_vp, c_vp],
     "ngp_composite_rays_train_backward": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                           c_vp, c_u32, c_u32, c_f32, c_vp, c_vp, c_vp],
+    "ngp_distortion_rays_train_forward": [c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_vp, c_vp],
+    "ngp_distortion_rays_train_backward": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_vp, c_vp],
     "ngp_march_rays": [c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_u32, c_u32, c_u32,
                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_grid_encode_forward_fused_tail": [c_vp, c_f32, c_vp, c_i32, c_vp, c_vp, c_u32, c_vp, c_u32, c_u32, c_u32,
@@ -162,6 +164,10 @@ SIGNATURES = {
                                       c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_nerf_composite_loss_depth_lists": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
                                             c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_nerf_composite_loss_dist": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
+                                     c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_nerf_composite_loss_dist_lists": [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_f32, c_vp,
+                                           c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_nerf_backward_join_dw": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp,
                                   c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_u32,
                                   c_u32, c_vp],
@@ -278,6 +284,12 @@ class DepthLossJob(ctypes.Structure):
     _fields_ = [("gt_depth", c_vp), ("color_weight", c_f32), ("depth_weight", c_f32), ("depth_min", c_f32),
                 ("depth_max", c_f32), ("out_depth", c_vp), ("loss_depth_ray", c_vp), ("ray_rows", c_vp),
                 ("live_cnt", c_vp), ("live_rows", c_vp), ("live_total", c_vp)]
+
+
+class DistLossJob(ctypes.Structure):
+    """ngp_dist_loss_job (include/ngp_hip.h): the distortion term's weight and
+    its optional per-ray output, of ngp_nerf_composite_loss_dist."""
+    _fields_ = [("weight", c_f32), ("loss_dist_ray", c_vp)]
 
 
 _lib = None

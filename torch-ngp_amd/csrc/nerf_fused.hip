@@ -16,7 +16,9 @@
 //                     composite backward, cast/sigmoid/trunc_exp backward ->
 //                     fp16 MLP-output grads; <true>: plus the masked L1
 //                     depth term and the colour / depth loss weights
-//                     (ngp_nerf_composite_loss_depth, utils.py:545-553, 951-954)
+//                     (ngp_nerf_composite_loss_depth, utils.py:545-553, 951-954);
+//                     <., true>: plus the distortion regulariser on the ray's
+//                     weights (ngp_nerf_composite_loss_dist)
 //   k_error_map_select / k_error_map_update   the reference's --error_map: a
 //                     weighted draw without replacement of the batch's map
 //                     cells, and the EMA of each ray's colour error into them
@@ -34,6 +36,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 
 namespace {
 
@@ -134,6 +137,27 @@ struct DepthArgs {
     float* loss_depth_ray;  // nullable [N]: ray n's unweighted depth term
 };
 
+// The distortion term (ngp_dist_loss_job; k_composite_loss<., true> only): the
+// O(n) form of sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i delta_i w_i^2 over the
+// ray's composite weights, m the composite's own t.
+struct DistArgs {
+    float weight;          // >= 0; 0: the term is computed and written, the loss and the gradients are without it
+    float* loss_dist_ray;  // nullable [N]: ray n's unweighted term
+};
+
+// One chunk's share of the distortion term: with mm = m - m_0 and the
+// exclusive prefixes W = sum_{j<i} w_j, WM = sum_{j<i} w_j mm_j (carried across
+// chunks in Wacc, WMacc), sum_i 2 w_i (mm_i W - WM) + 1/3 delta_i w_i^2.
+// Every lane of the wave takes part; an inactive lane has w = 0.
+NGP_DEV float dist_chunk(float w, float mm, float d0, float& Wacc, float& WMacc) {
+    const float wi = ngp_dpp::scan_incl(w), wmi = ngp_dpp::scan_incl(w * mm);
+    const float W = Wacc + __builtin_bit_cast(float, ngp_dpp::prev_lane(__builtin_bit_cast(uint32_t, wi)));
+    const float WM = WMacc + __builtin_bit_cast(float, ngp_dpp::prev_lane(__builtin_bit_cast(uint32_t, wmi)));
+    Wacc += lane63(wi);
+    WMacc += lane63(wmi);
+    return wave_sum(2.0f * w * (mm * W - WM) + (1.0f / 3.0f) * d0 * (w * w));
+}
+
 // One 64-sample chunk of a ray: per-lane sample data and the scanned quantities.
 struct Chunk {
     bool ok, active;                 // lane holds a sample / sample is before the early stop
@@ -204,8 +228,9 @@ NGP_DEV Chunk scan_chunk(const Raw& rw, uint32_t base, uint32_t num_steps, uint3
 constexpr uint32_t kLossPre = 4;
 
 // kDepth: the depth-supervised loss (DepthArgs); false is the colour-only
-// kernel, which reads nothing of `da`.
-template <bool kDepth>
+// kernel, which reads nothing of `da`. kDist: plus the distortion term
+// (DistArgs); false reads nothing of `di` and is the kernel without it.
+template <bool kDepth, bool kDist = false>
 __global__ void __launch_bounds__(kLossWaves * 64)
 k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ color_out,
                  const ngp_half* __restrict__ h_sigma, const float* __restrict__ deltas,
@@ -214,7 +239,7 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
                  StepState* __restrict__ st, ngp_half* __restrict__ grad_color_out,
                  ngp_half* __restrict__ grad_h, float* __restrict__ out_image,
                  float* __restrict__ out_ws, float* __restrict__ loss_ray, int32_t* __restrict__ ray_rows,
-                 int32_t* __restrict__ live_cnt, DepthArgs da) {
+                 int32_t* __restrict__ live_cnt, DepthArgs da, DistArgs di) {
     typedef _Float16 half8 __attribute__((ext_vector_type(8)));
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t n = blockIdx.x * kLossWaves + (threadIdx.x >> 6);
@@ -256,6 +281,10 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
     float Sk[kLossPre], tk[kLossPre];
     bool stopk[kLossPre];
     uint32_t nkept = 0;  // kept chunks scanned (the forward stopped in the last of them, or ran on)
+    // distortion term: the ray's value, its first midpoint (the value depends on
+    // differences of m only; the shift keeps the prefix products small) and
+    // the totals of w and w (m - m0) the backward needs
+    float dist = 0.0f, m0 = 0.0f, Wtot = 0.0f, WMtot = 0.0f;
     if (valid) {
         float S = 0.0f, tacc = 0.0f;
         bool stop = false;
@@ -273,6 +302,10 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
             b += wave_sum(c.w * c.c2);
             ws += wave_sum(c.w);
             d += wave_sum(c.w * c.t);
+            if constexpr (kDist) {
+                if (k == 0) m0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, c.t)));
+                dist += dist_chunk(c.w, c.t - m0, c.d0, Wtot, WMtot);
+            }
         }
         for (uint32_t base = 64 * kLossPre; !stop && base < num_steps; base += 64) {
             const Chunk c = scan_chunk(load_raw(sigma, color_out, deltas, h_sigma, offset, base, num_steps, lane),
@@ -282,6 +315,7 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
             b += wave_sum(c.w * c.c2);
             ws += wave_sum(c.w);
             d += wave_sum(c.w * c.t);
+            if constexpr (kDist) dist += dist_chunk(c.w, c.t - m0, c.d0, Wtot, WMtot);
         }
     }
     // ---- background blend + MSE (utils.py train_step) and its gradient
@@ -312,14 +346,22 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
         const float sgn = pd > gtd ? 1.0f : (pd < gtd ? -1.0f : 0.0f);
         if (mask && d >= 0.0f) gd = ((st->scale * da.dw) * la.inv_n) * sgn;
         if (lane == 0) {
-            loss_ray[n] = da.cw * (((e0 * e0 + e1 * e1) + e2 * e2) * la.inv_c) + da.dw * dep;
+            const float lr = da.cw * (((e0 * e0 + e1 * e1) + e2 * e2) * la.inv_c) + da.dw * dep;
+            // (distortion weight 0: the depth entry's value, a select and not + 0)
+            loss_ray[n] = kDist && di.weight != 0.0f ? lr + di.weight * dist : lr;
             if (da.out_depth) da.out_depth[index] = d;
             if (da.loss_depth_ray) da.loss_depth_ray[n] = dep;
         }
     }
     if (lane == 0) {
         // per-ray loss; summed by k_step_end (one reduction, no contended atomics)
-        if constexpr (!kDepth) loss_ray[n] = ((e0 * e0 + e1 * e1) + e2 * e2) * la.inv_c;
+        if constexpr (!kDepth) {
+            const float lr = ((e0 * e0 + e1 * e1) + e2 * e2) * la.inv_c;
+            loss_ray[n] = kDist && di.weight != 0.0f ? lr + di.weight * dist : lr;
+        }
+        if constexpr (kDist) {
+            if (di.loss_dist_ray) di.loss_dist_ray[n] = dist;
+        }
         if (out_image) {
             out_image[index * 3] = p0; out_image[index * 3 + 1] = p1; out_image[index * 3 + 2] = p2;
         }
@@ -330,6 +372,9 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
     const float G = ((kDepth ? st->scale * cw : st->scale) * la.inv_n) * la.inv_c;
     const float gr = G * (2.0f * e0), gg = G * (2.0f * e1), gb = G * (2.0f * e2);
     const float gws = -((gr * bg0 + gg * bg1) + gb * bg2);  // d/dws of image + (1 - ws) * bg
+    // distortion term: d loss / d dist (AMP-scaled), through weight -> mean over the N rays
+    float gdist = 0.0f;
+    if constexpr (kDist) gdist = (st->scale * di.weight) * la.inv_n;
 
     // ---- backward (composite_rays_train_backward) + activation backward
     if (!valid) {
@@ -344,6 +389,7 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
         return;
     }
     float S = 0.0f, tacc = 0.0f, rr = 0, rg = 0, rb = 0, rd = 0;
+    float rW = 0.0f, rWM = 0.0f, rgw = 0.0f;  // (distortion term) running sums of w, w (m - m0) and g w
     bool stopped = false;
     uint32_t nlive = 0;  // rows of this ray with a nonzero gradient so far (listed in ray_rows)
     for (uint32_t base = 0; base < num_steps; base += 64) {
@@ -395,6 +441,24 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
         const float pb = rb + scan_incl(c.w * c.c2, lane);
         const float pd = rd + scan_incl(c.w * c.t, lane);
         rr = lane63(pr); rg = lane63(pg); rb = lane63(pb); rd = lane63(pd);
+        // distortion term: the two prefixes again (not kept across the passes),
+        // g = d dist / d w, and the inclusive prefix of g w. The sum of g w over
+        // the samples behind is 2 dist minus that prefix: dist is homogeneous
+        // of degree 2 in w, so the whole sum is 2 dist, known since the forward.
+        float gdw = 0.0f, pgw = 0.0f;
+        if constexpr (kDist) {
+            const float mm = c.t - m0;
+            const float wi = scan_incl(c.w, lane), wmi = scan_incl(c.w * mm, lane);
+            const float W = rW + __builtin_bit_cast(float, ngp_dpp::prev_lane(__builtin_bit_cast(uint32_t, wi)));
+            const float WM = rWM + __builtin_bit_cast(float, ngp_dpp::prev_lane(__builtin_bit_cast(uint32_t, wmi)));
+            rW += lane63(wi);
+            rWM += lane63(wmi);
+            // m (W_< - W_>) + (WM_> - WM_<) with the suffixes from the totals, W_> = Wtot - W_< - w
+            // and WM_> = WMtot - WM_< - w m: the two w m products cancel
+            gdw = (2.0f / 3.0f) * c.d0 * c.w + 2.0f * (mm * ((W + W) - Wtot) + (WMtot - (WM + WM)));
+            pgw = rgw + scan_incl(c.active ? gdw * c.w : 0.0f, lane);
+            rgw = lane63(pgw);
+        }
         bool lv = false;
         if (c.ok) {
             const uint32_t i = offset + base + lane;
@@ -404,6 +468,10 @@ k_composite_loss(const float* __restrict__ sigma, const ngp_half* __restrict__ c
                 gs = c.d0 * (gr * (c.Tafter * c.c0 - (r - pr)) + gg * (c.Tafter * c.c1 - (g - pg)) +
                              gb * (c.Tafter * c.c2 - (b - pb)) + gd * (c.Tafter * c.t - (d - pd)) +
                              gws * (1 - ws));
+                // (weight 0: gs as it is, a select and not + 0)
+                if constexpr (kDist) {
+                    if (di.weight != 0.0f) gs += gdist * (c.d0 * (gdw * c.Tafter - ((dist + dist) - pgw)));
+                }
             }
             // rgbs.float() <- half, then sigmoid_backward(grad, y) = grad * (1 - y) * y (fp32 math)
             half8 o0 = {0, 0, 0, 0, 0, 0, 0, 0}, o1 = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -924,7 +992,7 @@ extern "C" int ngp_nerf_composite_loss(const float* sigma, const void* color_out
     k_composite_loss<false><<<ngp_div_up(N, kLossWaves), kLossWaves * 64, 0, ngp_stream(stream)>>>(
         sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
         static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
-        out_ws, loss_ray, nullptr, nullptr, DepthArgs{});
+        out_ws, loss_ray, nullptr, nullptr, DepthArgs{}, DistArgs{});
     return ngp_check_launch("nerf_composite_loss");
 }
 
@@ -958,7 +1026,7 @@ static int composite_loss_live_impl(const float* sigma, const void* color_out, c
     k_composite_loss<false><<<ngp_div_up(N, kLossWaves), kLossWaves * 64, 0, st>>>(
         sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
         static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
-        out_ws, loss_ray, ray_rows, live_cnt, DepthArgs{});
+        out_ws, loss_ray, ray_rows, live_cnt, DepthArgs{}, DistArgs{});
     if (compact)
         k_live_compact<<<ngp_div_up(N, kLiveRaysPerBlock), kLiveThreads, 0, st>>>(rays, live_cnt, ray_rows, N,
                                                                                   live_rows, live_total);
@@ -994,7 +1062,8 @@ static int composite_loss_depth_impl(const float* sigma, const void* color_out, 
                                      float T_thresh, float density_scale, const float* gt, uint32_t gt_channels,
                                      const float* bg, void* state, void* grad_color_out, void* grad_h_sigma,
                                      float* out_image, float* out_ws, float* loss_ray,
-                                     const ngp_depth_loss_job* job, bool compact, void* stream);
+                                     const ngp_depth_loss_job* job, const ngp_dist_loss_job* dist, bool compact,
+                                     void* stream);
 
 extern "C" int ngp_nerf_composite_loss_depth(const float* sigma, const void* color_out, const void* h_sigma,
                                              const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
@@ -1005,7 +1074,7 @@ extern "C" int ngp_nerf_composite_loss_depth(const float* sigma, const void* col
                                              void* stream) {
     return composite_loss_depth_impl(sigma, color_out, h_sigma, deltas, rays, M, N, T_thresh, density_scale, gt,
                                      gt_channels, bg, state, grad_color_out, grad_h_sigma, out_image, out_ws,
-                                     loss_ray, job, true, stream);
+                                     loss_ray, job, nullptr, true, stream);
 }
 
 extern "C" int ngp_nerf_composite_loss_depth_lists(const float* sigma, const void* color_out, const void* h_sigma,
@@ -1019,16 +1088,57 @@ extern "C" int ngp_nerf_composite_loss_depth_lists(const float* sigma, const voi
                 "composite_loss_depth_lists: the job's ray_rows [M] and live_cnt [N] are required");
     return composite_loss_depth_impl(sigma, color_out, h_sigma, deltas, rays, M, N, T_thresh, density_scale, gt,
                                      gt_channels, bg, state, grad_color_out, grad_h_sigma, out_image, out_ws,
-                                     loss_ray, job, false, stream);
+                                     loss_ray, job, nullptr, false, stream);
 }
 
-// compact false (.._depth_lists): the job's live_rows / live_total are not used
+// The depth entries with the distortion term (ngp_dist_loss_job). A job with
+// the colour-only defaults and no depth outputs runs the kernel without the
+// depth form (the depth form gives the same bits there).
+static int check_dist_job(const ngp_dist_loss_job* dist) {
+    NGP_REQUIRE(dist, NGP_ERR_ARG, "composite_loss_dist: null dist job");
+    NGP_REQUIRE(dist->weight >= 0.0f && std::isfinite(dist->weight), NGP_ERR_ARG,
+                "composite_loss_dist: the weight must be finite and >= 0");
+    return NGP_OK;
+}
+
+extern "C" int ngp_nerf_composite_loss_dist(const float* sigma, const void* color_out, const void* h_sigma,
+                                            const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
+                                            float T_thresh, float density_scale, const float* gt,
+                                            uint32_t gt_channels, const float* bg, void* state,
+                                            void* grad_color_out, void* grad_h_sigma, float* out_image,
+                                            float* out_ws, float* loss_ray, const ngp_depth_loss_job* job,
+                                            const ngp_dist_loss_job* dist, void* stream) {
+    if (int e = check_dist_job(dist)) return e;
+    return composite_loss_depth_impl(sigma, color_out, h_sigma, deltas, rays, M, N, T_thresh, density_scale, gt,
+                                     gt_channels, bg, state, grad_color_out, grad_h_sigma, out_image, out_ws,
+                                     loss_ray, job, dist, true, stream);
+}
+
+extern "C" int ngp_nerf_composite_loss_dist_lists(const float* sigma, const void* color_out, const void* h_sigma,
+                                                  const float* deltas, const int32_t* rays, uint32_t M,
+                                                  uint32_t N, float T_thresh, float density_scale,
+                                                  const float* gt, uint32_t gt_channels, const float* bg,
+                                                  void* state, void* grad_color_out, void* grad_h_sigma,
+                                                  float* out_image, float* out_ws, float* loss_ray,
+                                                  const ngp_depth_loss_job* job, const ngp_dist_loss_job* dist,
+                                                  void* stream) {
+    if (int e = check_dist_job(dist)) return e;
+    NGP_REQUIRE(job && job->ray_rows && job->live_cnt, NGP_ERR_ARG,
+                "composite_loss_dist_lists: the job's ray_rows [M] and live_cnt [N] are required");
+    return composite_loss_depth_impl(sigma, color_out, h_sigma, deltas, rays, M, N, T_thresh, density_scale, gt,
+                                     gt_channels, bg, state, grad_color_out, grad_h_sigma, out_image, out_ws,
+                                     loss_ray, job, dist, false, stream);
+}
+
+// compact false (.._depth_lists): the job's live_rows / live_total are not used.
+// dist: null for the depth entries
 static int composite_loss_depth_impl(const float* sigma, const void* color_out, const void* h_sigma,
                                      const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
                                      float T_thresh, float density_scale, const float* gt, uint32_t gt_channels,
                                      const float* bg, void* state, void* grad_color_out, void* grad_h_sigma,
                                      float* out_image, float* out_ws, float* loss_ray,
-                                     const ngp_depth_loss_job* job, bool compact, void* stream) {
+                                     const ngp_depth_loss_job* job, const ngp_dist_loss_job* dist, bool compact,
+                                     void* stream) {
     NGP_REQUIRE(job, NGP_ERR_ARG, "composite_loss_depth: null job");
     NGP_REQUIRE(loss_ray, NGP_ERR_ARG, "composite_loss_depth: loss_ray [N] buffer required");
     NGP_REQUIRE(gt_channels == 3 || gt_channels == 4, NGP_ERR_ARG, "composite_loss_depth: gt must be RGB or RGBA");
@@ -1054,10 +1164,27 @@ static int composite_loss_depth_impl(const float* sigma, const void* color_out, 
     la.gt_channels = gt_channels;
     const DepthArgs da{job->gt_depth, job->color_weight, job->depth_weight, job->depth_min, job->depth_max,
                        job->out_depth, job->loss_depth_ray};
-    k_composite_loss<true><<<ngp_div_up(N, kLossWaves), kLossWaves * 64, 0, st>>>(
-        sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
-        static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
-        out_ws, loss_ray, job->ray_rows, job->live_cnt, da);
+    const dim3 grid(ngp_div_up(N, kLossWaves)), block(kLossWaves * 64);
+    if (!dist) {
+        k_composite_loss<true><<<grid, block, 0, st>>>(
+            sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
+            static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
+            out_ws, loss_ray, job->ray_rows, job->live_cnt, da, DistArgs{});
+    } else {
+        const DistArgs di{dist->weight, dist->loss_dist_ray};
+        const bool plain = job->color_weight == 1.0f && job->depth_weight == 0.0f && !job->gt_depth &&
+                           !job->out_depth && !job->loss_depth_ray;
+        if (plain)
+            k_composite_loss<false, true><<<grid, block, 0, st>>>(
+                sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
+                static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
+                out_ws, loss_ray, job->ray_rows, job->live_cnt, DepthArgs{}, di);
+        else
+            k_composite_loss<true, true><<<grid, block, 0, st>>>(
+                sigma, (const ngp_half*)color_out, (const ngp_half*)h_sigma, deltas, rays, M, N, gt, bg, la,
+                static_cast<StepState*>(state), (ngp_half*)grad_color_out, (ngp_half*)grad_h_sigma, out_image,
+                out_ws, loss_ray, job->ray_rows, job->live_cnt, da, di);
+    }
     if (live && compact)
         k_live_compact<<<ngp_div_up(N, kLiveRaysPerBlock), kLiveThreads, 0, st>>>(rays, job->live_cnt, job->ray_rows,
                                                                                   N, job->live_rows, job->live_total);

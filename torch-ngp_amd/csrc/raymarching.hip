@@ -1142,6 +1142,98 @@ k_composite_train_bwd(const float* __restrict__ grad_weights_sum, const float* _
     }
 }
 
+// ---- distortion_rays_train (one thread per ray) -----------------------------------
+// The distortion regulariser of mip-NeRF 360 in its O(n) form (the reference's
+// loss.py EffDistLoss) on the training composite's weights: w_i = alpha_i T_i
+// with the composite's serial T *= 1 - alpha and its stop rule (the stopping
+// sample included, 0 behind it), m_i the composite's t, delta_i = deltas[i][0]:
+//   dist = 2 sum_i w_i (m_i W_<i - WM_<i) + 1/3 sum_i delta_i w_i^2
+// m is taken relative to the ray's first midpoint (the value depends on
+// differences of m only). The reference-API op: the serial form, as the
+// composite above keeps the serial recurrence; the fused step has the term in
+// k_composite_loss on wave scans.
+__global__ void __launch_bounds__(128)
+k_distortion_train_fwd(const float* __restrict__ sigmas, const float* __restrict__ deltas,
+                       const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh,
+                       float* __restrict__ dist) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3];
+    const uint32_t offset = (uint32_t)rays[n * 3 + 1];
+    const uint32_t num_steps = (uint32_t)rays[n * 3 + 2];
+    float acc = 0.0f;
+    if (num_steps != 0 && offset + num_steps <= M) {
+        const float m0 = deltas[(size_t)offset * 2 + 1];
+        float T = 1.0f, t = 0.0f, W = 0.0f, WM = 0.0f;
+        for (uint32_t k = 0; k < num_steps; ++k) {
+            const uint32_t i = offset + k;
+            const float d0 = deltas[(size_t)i * 2];
+            const float a = 1.0f - expf(-sigmas[i] * d0);
+            const float w = a * T;
+            t += deltas[(size_t)i * 2 + 1];
+            const float mm = t - m0;
+            acc += 2.0f * w * (mm * W - WM) + (1.0f / 3.0f) * d0 * (w * w);
+            W += w;
+            WM += w * mm;
+            T *= 1.0f - a;
+            if (T < T_thresh) break;
+        }
+    }
+    dist[index] = acc;
+}
+
+// d dist / d w_i = g_i = 2/3 delta_i w_i + 2 (m_i (W_<i - W_>i) + (WM_>i - WM_<i)),
+// and through the composite's chain d dist / d sigma_j =
+// delta_j (g_j Tafter_j - sum_{i>j} g_i w_i); the sum over all i of g_i w_i is
+// 2 dist (dist is homogeneous of degree 2 in w), so the suffix is 2 dist minus
+// the running prefix. Pass 1: the totals of w and w m; pass 2: the gradients.
+// Rows past the stop (and a ray without a composite) are left as the caller
+// zeroed them.
+__global__ void __launch_bounds__(128)
+k_distortion_train_bwd(const float* __restrict__ grad_dist, const float* __restrict__ sigmas,
+                       const float* __restrict__ deltas, const int32_t* __restrict__ rays,
+                       const float* __restrict__ dist, uint32_t M, uint32_t N, float T_thresh,
+                       float* __restrict__ grad_sigmas) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3];
+    const uint32_t offset = (uint32_t)rays[n * 3 + 1];
+    const uint32_t num_steps = (uint32_t)rays[n * 3 + 2];
+    if (num_steps == 0 || offset + num_steps > M) return;
+    const float m0 = deltas[(size_t)offset * 2 + 1];
+    float T = 1.0f, t = 0.0f, Wtot = 0.0f, WMtot = 0.0f;
+    for (uint32_t k = 0; k < num_steps; ++k) {
+        const uint32_t i = offset + k;
+        const float a = 1.0f - expf(-sigmas[i] * deltas[(size_t)i * 2]);
+        const float w = a * T;
+        t += deltas[(size_t)i * 2 + 1];
+        Wtot += w;
+        WMtot += w * (t - m0);
+        T *= 1.0f - a;
+        if (T < T_thresh) break;
+    }
+    const float go = grad_dist[index], two_dist = 2.0f * dist[index];
+    T = 1.0f;
+    t = 0.0f;
+    float W = 0.0f, WM = 0.0f, pgw = 0.0f;
+    for (uint32_t k = 0; k < num_steps; ++k) {
+        const uint32_t i = offset + k;
+        const float d0 = deltas[(size_t)i * 2];
+        const float a = 1.0f - expf(-sigmas[i] * d0);
+        const float w = a * T;
+        t += deltas[(size_t)i * 2 + 1];
+        const float mm = t - m0;
+        // (W_> = Wtot - W_< - w and WM_> = WMtot - WM_< - w m: the two w m products cancel)
+        const float g = (2.0f / 3.0f) * d0 * w + 2.0f * (mm * ((W + W) - Wtot) + (WMtot - (WM + WM)));
+        pgw += g * w;
+        W += w;
+        WM += w * mm;
+        T *= 1.0f - a;
+        grad_sigmas[i] = go * (d0 * (g * T - (two_dist - pgw)));
+        if (T < T_thresh) break;
+    }
+}
+
 __global__ void __launch_bounds__(128)
 k_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* __restrict__ rays_alive,
              const float* __restrict__ rays_t, const float* __restrict__ rays_o,
@@ -1644,6 +1736,28 @@ extern "C" int ngp_composite_rays_train_backward(const float* grad_weights_sum,
         grad_weights_sum, grad_depth, grad_image, sigmas, rgbs, deltas, rays, weights_sum, depth,
         image, M, N, T_thresh, grad_sigmas, grad_rgbs);
     return ngp_check_launch("composite_rays_train_backward");
+}
+
+extern "C" int ngp_distortion_rays_train_forward(const float* sigmas, const float* deltas, const int32_t* rays,
+                                                 uint32_t M, uint32_t N, float T_thresh, float* dist,
+                                                 void* stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(sigmas && deltas && rays && dist, NGP_ERR_ARG, "distortion_rays_train_forward: null buffer");
+    k_distortion_train_fwd<<<ngp_div_up(N, 128), 128, 0, ngp_stream(stream)>>>(sigmas, deltas, rays, M, N,
+                                                                               T_thresh, dist);
+    return ngp_check_launch("distortion_rays_train_forward");
+}
+
+extern "C" int ngp_distortion_rays_train_backward(const float* grad_dist, const float* sigmas,
+                                                  const float* deltas, const int32_t* rays, const float* dist,
+                                                  uint32_t M, uint32_t N, float T_thresh, float* grad_sigmas,
+                                                  void* stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(grad_dist && sigmas && deltas && rays && dist && grad_sigmas, NGP_ERR_ARG,
+                "distortion_rays_train_backward: null buffer");
+    k_distortion_train_bwd<<<ngp_div_up(N, 128), 128, 0, ngp_stream(stream)>>>(grad_dist, sigmas, deltas, rays, dist,
+                                                                               M, N, T_thresh, grad_sigmas);
+    return ngp_check_launch("distortion_rays_train_backward");
 }
 
 extern "C" int ngp_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive,

@@ -12,6 +12,11 @@ trainer.save_mesh (main_nerf.py:190 / :241). --depth_loss_weight > 0 adds the
 reference's depth supervision on scenes whose frames carry a dep_path: the
 loss is color_loss_weight * rgb + depth_loss_weight * dep (nerf/utils.py
 :545-553, 951-954), the depths gathered on the device beside the colours.
+--dist_loss_weight W > 0 adds W times the mean over a
+batch's rays of the distortion regulariser (the reference's loss.py
+EffDistLoss on the composite's own weights), formed
+inside the composite launch; the log line then carries `dist`, and the eval
+split's mean ray distortion is printed after the PSNR.
 --error_map is the reference's importance sampling (nerf/utils.py:101-113,
 578-600): a coarse error image per training view (--error_map_res cells a
 side, the reference's 128), the batch's pixels drawn from it without
@@ -65,6 +70,9 @@ def get_parser():
     p.add_argument("--depth_loss_weight", type=float, default=0.0,
                    help="weight of the masked L1 depth loss (needs a dep_path per frame)")
     p.add_argument("--color_loss_weight", type=float, default=1.0, help="weight of the colour MSE")
+    p.add_argument("--dist_loss_weight", type=float, default=0.0,
+                   help="weight of the distortion regulariser on each ray's composite weights (the reference's "
+                        "loss.py EffDistLoss; 0: off)")
     p.add_argument("--error_map", action="store_true", help="use error map to sample rays")
     p.add_argument("--error_map_res", type=int, default=128,
                    help="cells a side of each view's error map (1..128; needs num_rays <= its square)")
@@ -207,7 +215,7 @@ def main(argv=None):
 
     import torch
 
-    from nerf.eval import Validator, depth_error, psnr
+    from nerf.eval import Validator, depth_error, psnr, ray_distortion
     from nerf.fused import FusedTrainer
     from nerf.fused_render import FusedRenderer
     from nerf.network_ff import NeRFNetwork
@@ -242,7 +250,8 @@ def main(argv=None):
     try:
         ft = FusedTrainer(model, train, M=M, lr=opt.lr, iters=opt.iters, max_steps=opt.max_steps,
                           dt_gamma=opt.dt_gamma, seed=opt.seed, depth_loss_weight=opt.depth_loss_weight,
-                          color_loss_weight=opt.color_loss_weight, ema_decay=opt.ema_decay)
+                          color_loss_weight=opt.color_loss_weight, ema_decay=opt.ema_decay,
+                          dist_loss_weight=opt.dist_loss_weight)
     except ValueError as e:  # e.g. a depth weight on a scene without depth maps
         sys.exit(f"[main_nerf] {e}")
     ema = opt.ema_decay is not None
@@ -348,8 +357,11 @@ def main(argv=None):
         over += ft.over_budget(n)
         checked += n
         if done % log_every == 0 or done == opt.iters:
-            dep = ft.last_depth_loss  # None: the colour-only loss
-            terms = "" if dep is None else f" (rgb {ft.last_color_loss:.6f}, dep {dep:.6f})"
+            dep, dst = ft.last_depth_loss, ft.last_dist_loss  # None: the term is off
+            terms = ""
+            if dep is not None or dst is not None:
+                terms = (f" (rgb {ft.last_color_loss:.6f}" + ("" if dep is None else f", dep {dep:.6f}")
+                         + ("" if dst is None else f", dist {dst:.6f}") + ")")
             print(f"[main_nerf] step {done}/{opt.iters} loss {ft.last_loss:.6f}{terms} "
                   f"({time.perf_counter() - t0:.1f} s)")
     ft.flush()
@@ -381,6 +393,13 @@ def main(argv=None):
         errs = [e for e in errs if math.isfinite(e)]
         mean_depth = sum(errs) / len(errs) if errs else float("nan")
         print(f"[main_nerf] depth error {mean_depth:.6f} over {val.poses.shape[0]} {split} images")
+    # ... and, with the distortion regulariser, what it regularises: the views' mean ray distortion
+    mean_dist = None
+    if opt.dist_loss_weight > 0:
+        dists = [ray_distortion(model, val, i, dt_gamma=opt.dt_gamma, max_steps=opt.max_steps)
+                 for i in range(val.poses.shape[0])]
+        mean_dist = sum(dists) / len(dists)
+        print(f"[main_nerf] ray distortion {mean_dist:.6f} over {val.poses.shape[0]} {split} images")
     model.train()
 
     os.makedirs(ckpt_dir, exist_ok=True)
@@ -391,7 +410,8 @@ def main(argv=None):
     print(f"[main_nerf] checkpoint {ckpt}")
     result = {"psnr": mean_psnr, "loss": ft.last_loss, "over_budget": int(over.item()), "checkpoint": ckpt,
               "seconds": secs, "depth_error": mean_depth, "start_step": start, "epoch": epoch,
-              "valid_psnr": valid_psnr, "best_checkpoint": best_ckpt}
+              "valid_psnr": valid_psnr, "best_checkpoint": best_ckpt, "dist_loss": ft.last_dist_loss,
+              "ray_distortion": mean_dist}
     if opt.save_mesh:
         ft.workspace = opt.workspace
         path, nv, nt = ft.save_mesh(resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)

@@ -79,6 +79,35 @@ def depth_error(model, dataset, index, dt_gamma=0.0, max_steps=1024, chunk=4096)
     return float(err.mean().item()) if err.numel() else float("nan")
 
 
+@torch.no_grad()
+def ray_distortion(model, dataset, index, dt_gamma=0.0, max_steps=1024, chunk=4096):
+    """Mean distortion term (the reference's loss.py EffDistLoss on the
+    composite's weights, in ngp units; 0 for a ray without samples) over all
+    H * W rays of pose `index`: the quantity dist_loss_weight regularises, so it
+    is computed with the training composite through the reference-API render
+    (perturb=False, force_all_rays=True, dist_loss=True), in the manner of
+    depth_error."""
+    H, W = int(dataset.H), int(dataset.W)
+    rays = get_rays(dataset.poses[index:index + 1], dataset.intrinsics, H, W, -1)
+    was_training = model.training
+    model.train()  # the training composite (march_rays_train + distortion_rays_train)
+    local_step, counts = model.local_step, model.step_counter.clone()
+    total = torch.zeros((), dtype=torch.float64, device=rays["rays_o"].device)
+    try:
+        for a in range(0, H * W, chunk):
+            with torch.autocast("cuda", dtype=torch.float16):
+                out = model.render(rays["rays_o"][:, a:a + chunk], rays["rays_d"][:, a:a + chunk], staged=False,
+                                   bg_color=1, perturb=False, force_all_rays=True, dt_gamma=dt_gamma,
+                                   max_steps=max_steps, dist_loss=True)
+            total += out["distortion"].double().sum()
+    finally:
+        # (run_cuda counted training steps: the trainer's bookkeeping stays as it was)
+        model.local_step = local_step
+        model.step_counter.copy_(counts)
+        model.train(was_training)
+    return float(total.item()) / (H * W)
+
+
 class Validator:
     """The reference's evaluate_one_epoch (nerf/utils.py:1075-1173) over a
     dataset's views without leaving the device: a FrameRenderer over the

@@ -130,7 +130,8 @@ class FusedTrainer:
     def __init__(self, model, dataset, M, lr=1e-2, iters=30000, max_steps=1024, T_thresh=1e-4,
                  dt_gamma=0.0, seed=0, betas=(0.9, 0.99), eps=1e-15, init_scale=65536.0,
                  growth_interval=2000, distributed=False, grid_timing=False, options=None,
-                 depth_loss_weight=0.0, color_loss_weight=1.0, error_map=None, ema_decay=None):
+                 depth_loss_weight=0.0, color_loss_weight=1.0, error_map=None, ema_decay=None,
+                 dist_loss_weight=0.0):
         """distributed: ray-sharded data parallelism over the initialised
         torch.distributed group: each rank draws its own rays; the flat fp16
         gradient is averaged with one RCCL reduce-scatter, each rank's Adam
@@ -161,7 +162,13 @@ class FusedTrainer:
         (torch_ema through Trainer(ema_decay=0.95)): a
         float32 shadow of flat_param, updated by `ema_update()` (the caller's,
         once per epoch), read through `ema_params()`, saved and restored with
-        the checkpoint. None: no shadow and no launch anywhere. World 1 only."""
+        the checkpoint. None: no shadow and no launch anywhere. World 1 only.
+        dist_loss_weight: adds dist_loss_weight * the mean over the N rays of the
+        distortion regulariser (the reference's loss.py EffDistLoss on the
+        composite's own weights) to the loss; the term and
+        its gradient are formed inside the composite launch
+        (ngp_nerf_composite_loss_dist). 0: the step without it, launch for
+        launch. World 1 only."""
         opts = dict(DEFAULT_OPTIONS)
         for k, v in (options or {}).items():
             if k not in opts:
@@ -190,6 +197,12 @@ class FusedTrainer:
         if self.depth_loss_weight > 0 and depths is None:
             raise ValueError("FusedTrainer: depth_loss_weight > 0 needs a dataset with depth maps (dataset.depths: "
                              "a dep_path per frame, nerf.provider.NeRFDataset); this one has none")
+        self.dist_loss_weight = float(dist_loss_weight)
+        if not self.dist_loss_weight >= 0 or self.dist_loss_weight == float("inf"):
+            raise ValueError(f"FusedTrainer: dist_loss_weight must be finite and not negative, got {dist_loss_weight}")
+        if self.dist_loss_weight > 0 and distributed:
+            raise ValueError("FusedTrainer: dist_loss_weight is single-process only: the term's mean is over one "
+                             "rank's rays and has not been tested under data parallelism (distributed=True)")
         if ema_decay is not None:
             if distributed:
                 raise ValueError("FusedTrainer: ema_decay is single-process only: each rank of a data-parallel "
@@ -563,6 +576,26 @@ class FusedTrainer:
             self._loss_job_live = lj_live = nat.DepthLossJob.from_buffer_copy(lj)
             lj_live.ray_rows, lj_live.live_cnt = nat.ptr(lb["ray_rows"]), nat.ptr(lb["cnt"])
             lj_live.live_rows, lj_live.live_total = nat.ptr(lb["rows"]), nat.ptr(lb["total"])
+        # distortion regulariser: the composite's entry with the term, on the depth
+        # job (the colour-only defaults when the loss has no depth form)
+        self._dist_job = None
+        if self.dist_loss_weight > 0:
+            self.loss_dist_ray = z(N)
+            dj = nat.DistLossJob()
+            dj.weight, dj.loss_dist_ray = self.dist_loss_weight, nat.ptr(self.loss_dist_ray)
+            self._dist_job = dj
+            if self._loss_job is not None:
+                base = self._loss_job
+            else:
+                base = nat.DepthLossJob()
+                base.color_weight, base.depth_weight = 1.0, 0.0
+                base.depth_min, base.depth_max = float(model.min_near), float(model.bound)
+            self._dist_base = base
+            if self._live:
+                lb = self._live_bufs
+                self._dist_base_live = bl = nat.DepthLossJob.from_buffer_copy(base)
+                bl.ray_rows, bl.live_cnt = nat.ptr(lb["ray_rows"]), nat.ptr(lb["cnt"])
+                bl.live_rows, bl.live_total = nat.ptr(lb["rows"]), nat.ptr(lb["total"])
         self.graph = None
         self.graph_multi, self._multi = None, 1  # capture(multi=S): S step bodies in one graph
         # data parallel over RCCL: the whole step is captured, collectives included
@@ -1137,7 +1170,17 @@ class FusedTrainer:
         # error-map sampling: the composite also writes its image, which the map's update reads
         img_out = P(self.out_image) if self._emap is not None or self._bg else None
         ws_out = P(self.out_ws) if self._bg else None  # (a background model's backward reads both)
-        if self._loss_job is not None:
+        if self._dist_job is not None:
+            # the distortion regulariser on top of the depth form's loss: one entry for both row forms
+            job = self._dist_base_live if live else self._dist_base
+            entry = lib.ngp_nerf_composite_loss_dist_lists if live and self._join else lib.ngp_nerf_composite_loss_dist
+            chk(entry(P(self.sigma), P(self.color_out), P(self.h_sigma), P(self.deltas),
+                      P(self.rays), M, N, self.T_thresh, float(m.density_scale),
+                      P(self.rgba), 4, P(self.bg), P(self.state), P(self.g_color_out),
+                      P(self.g_h), img_out, ws_out, P(self.loss_ray), ctypes.byref(job),
+                      ctypes.byref(self._dist_job), s),
+                "composite_loss_dist")
+        elif self._loss_job is not None:
             # the depth-supervised loss (and its weights): one entry for both row forms
             job = self._loss_job_live if live else self._loss_job
             entry = lib.ngp_nerf_composite_loss_depth_lists if live and self._join else lib.ngp_nerf_composite_loss_depth
@@ -1702,15 +1745,29 @@ class FusedTrainer:
         return float(self.loss_depth_ray.mean().item())
 
     @property
+    def last_dist_loss(self):
+        """The last step's unweighted distortion term, the mean over its N rays
+        (`last_loss` holds dist_loss_weight times it); None when the term is off."""
+        if self._dist_job is None:
+            return None
+        self.flush()
+        return float(self.loss_dist_ray.mean().item())
+
+    @property
     def last_color_loss(self):
         """The last step's unweighted colour term (the MSE), from the weighted
-        total and the depth term; None for the colour-only loss (`last_loss` is
-        it), nan when color_loss_weight is 0."""
-        if self._loss_job is None:
+        total, the depth term and the distortion term; None for the colour-only
+        loss (`last_loss` is it), nan when color_loss_weight is 0."""
+        if self._loss_job is None and self._dist_job is None:
             return None
         if self.color_loss_weight == 0:
             return float("nan")
-        return (self.last_loss - self.depth_loss_weight * self.last_depth_loss) / self.color_loss_weight
+        rest = self.last_loss
+        if self._loss_job is not None:
+            rest -= self.depth_loss_weight * self.last_depth_loss
+        if self._dist_job is not None:
+            rest -= self.dist_loss_weight * self.last_dist_loss
+        return rest / self.color_loss_weight
 
     @property
     def scale(self):

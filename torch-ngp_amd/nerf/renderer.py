@@ -160,8 +160,10 @@ class NeRFRenderer(nn.Module):
 
     # -------------------------------------------------------------- HIP path
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False,
-                 force_all_rays=False, max_steps=1024, T_thresh=1e-4, **kwargs):
-        """Density-grid ray marching (renderer.py:257-431, upstream semantics)."""
+                 force_all_rays=False, max_steps=1024, T_thresh=1e-4, dist_loss=False, **kwargs):
+        """Density-grid ray marching (renderer.py:257-431, upstream semantics).
+        dist_loss (training mode): also results["distortion"], each ray's
+        distortion term (raymarching.distortion_rays_train)."""
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)
@@ -190,6 +192,8 @@ class NeRFRenderer(nn.Module):
             sigmas = self.density_scale * sigmas
             weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays,
                                                                          T_thresh)
+            if dist_loss:
+                results["distortion"] = raymarching.distortion_rays_train(sigmas, deltas, rays, T_thresh)
             image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
             # the composite's depth in ngp units, what depth supervision compares (renderer.py:369)
             results["depth_bound_scale"] = torch.clamp(depth, min=0).view(*prefix)

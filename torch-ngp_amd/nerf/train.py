@@ -39,13 +39,17 @@ def average_gradients(params, group=None):
 class Trainer:
     def __init__(self, model, dataset, lr=1e-2, iters=30000, fp16=True, dt_gamma=0.0,
                  max_steps=1024, update_extra_interval=16, update_density=True,
-                 distributed=False, depth_loss_weight=0.0, color_loss_weight=1.0, perturb=True):
+                 distributed=False, depth_loss_weight=0.0, color_loss_weight=1.0, perturb=True,
+                 dist_loss_weight=0.0):
         """depth_loss_weight, color_loss_weight: the reference's pixel loss
         color_loss_weight * rgb + depth_loss_weight * dep (nerf/utils.py:951-954)
         on batches that carry "depths" (:545-553). perturb: the march's jitter
         (off for comparisons on a fixed batch). A dataset with an `error_map`
         (NeRFDataset(error_map=True)) draws its batches from it, and each
-        ray's colour MSE is folded back into its cell (utils.py:578-600)."""
+        ray's colour MSE is folded back into its cell (utils.py:578-600).
+        dist_loss_weight: adds dist_loss_weight * the mean over the rays of the
+        distortion regulariser (the reference's loss.py EffDistLoss on the
+        composite's weights, raymarching.distortion_rays_train)."""
         self.model = model
         self.dataset = dataset
         self.fp16 = fp16
@@ -54,6 +58,10 @@ class Trainer:
         self.depth_loss_weight, self.color_loss_weight = float(depth_loss_weight), float(color_loss_weight)
         self.perturb = bool(perturb)
         self.last_depth_loss = None
+        self.dist_loss_weight = float(dist_loss_weight)
+        if self.dist_loss_weight < 0:
+            raise ValueError("Trainer: dist_loss_weight must not be negative")
+        self.last_dist_loss = None
         self.update_extra_interval = update_extra_interval
         self.update_density = update_density
         self.distributed = distributed and dist.is_available() and dist.is_initialized()
@@ -82,7 +90,8 @@ class Trainer:
                             cache_enabled=self.graph is None and self.static is None):
             outputs = self.model.render(data["rays_o"], data["rays_d"], staged=False,
                                         bg_color=bg_color, perturb=self.perturb, force_all_rays=False,
-                                        dt_gamma=self.dt_gamma, max_steps=self.max_steps)
+                                        dt_gamma=self.dt_gamma, max_steps=self.max_steps,
+                                        **({"dist_loss": True} if self.dist_loss_weight > 0 else {}))
             pred_rgb = outputs["image"]
             loss_ray = ((pred_rgb - gt_rgb) ** 2).mean(-1)  # [B, N]
             loss = loss_ray.mean()
@@ -100,6 +109,10 @@ class Trainer:
                 loss = self.color_loss_weight * loss + self.depth_loss_weight * dep
             elif self.color_loss_weight != 1:
                 loss = self.color_loss_weight * loss
+            if self.dist_loss_weight > 0:
+                dist_term = outputs["distortion"].mean()
+                self.last_dist_loss = dist_term.detach()
+                loss = loss + self.dist_loss_weight * dist_term
         self.scaler.scale(loss).backward()
         return loss
 

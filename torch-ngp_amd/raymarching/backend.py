@@ -104,6 +104,25 @@ def composite_rays_train_backward(grad_weights_sum, grad_depth, grad_image, sigm
         nat.stream_of(sigmas)), "composite_rays_train_backward")
 
 
+def distortion_rays_train_forward(sigmas, deltas, rays, M, N, T_thresh, dist):
+    for t, n in ((sigmas, "sigmas"), (deltas, "deltas"), (dist, "dist")):
+        _f(t, n)
+    _i(rays, "rays")
+    nat.check(nat.lib().ngp_distortion_rays_train_forward(
+        nat.ptr(sigmas), nat.ptr(deltas), nat.ptr(rays), M, N, float(T_thresh), nat.ptr(dist),
+        nat.stream_of(sigmas)), "distortion_rays_train_forward")
+
+
+def distortion_rays_train_backward(grad_dist, sigmas, deltas, rays, dist, M, N, T_thresh, grad_sigmas):
+    for t, n in ((grad_dist, "grad_dist"), (sigmas, "sigmas"), (deltas, "deltas"), (dist, "dist"),
+                 (grad_sigmas, "grad_sigmas")):
+        _f(t, n)
+    _i(rays, "rays")
+    nat.check(nat.lib().ngp_distortion_rays_train_backward(
+        nat.ptr(grad_dist), nat.ptr(sigmas), nat.ptr(deltas), nat.ptr(rays), nat.ptr(dist), M, N,
+        float(T_thresh), nat.ptr(grad_sigmas), nat.stream_of(sigmas)), "distortion_rays_train_backward")
+
+
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C,
                H, grid, near, far, xyzs, dirs, deltas, noises):
     for t, n in ((rays_t, "rays_t"), (rays_o, "rays_o"), (rays_d, "rays_d"), (near, "nears"),
@@ -135,7 +154,8 @@ _backend = types.SimpleNamespace(
     morton3D_invert=morton3D_invert, packbits=packbits, march_rays_train=march_rays_train,
     composite_rays_train_forward=composite_rays_train_forward,
     composite_rays_train_backward=composite_rays_train_backward, march_rays=march_rays,
-    composite_rays=composite_rays,
+    composite_rays=composite_rays, distortion_rays_train_forward=distortion_rays_train_forward,
+    distortion_rays_train_backward=distortion_rays_train_backward,
 )
 
 __all__ = ["_backend"]

@@ -189,6 +189,37 @@ class _composite_rays_train(Function):
 composite_rays_train = _composite_rays_train.apply
 
 
+class _distortion_rays_train(Function):
+    @staticmethod
+    @_fwd32
+    def forward(ctx, sigmas, deltas, rays, T_thresh=1e-4):
+        """The distortion regulariser (the reference's loss.py EffDistLoss) of each
+        ray's training-composite weights, in ngp units -> dist [N] by ray index."""
+        sigmas = sigmas.contiguous()
+        deltas = deltas.contiguous()
+        M = sigmas.shape[0]
+        N = rays.shape[0]
+        dist = torch.empty(N, dtype=sigmas.dtype, device=sigmas.device)
+        _backend.distortion_rays_train_forward(sigmas, deltas, rays, M, N, T_thresh, dist)
+        ctx.save_for_backward(sigmas, deltas, rays, dist)
+        ctx.dims = [M, N, T_thresh]
+        return dist
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad_dist):
+        grad_dist = grad_dist.contiguous()
+        sigmas, deltas, rays, dist = ctx.saved_tensors
+        M, N, T_thresh = ctx.dims
+        grad_sigmas = torch.zeros_like(sigmas)
+        _backend.distortion_rays_train_backward(grad_dist, sigmas, deltas, rays, dist, M, N, T_thresh,
+                                                grad_sigmas)
+        return grad_sigmas, None, None, None
+
+
+distortion_rays_train = _distortion_rays_train.apply
+
+
 class _march_rays(Function):
     @staticmethod
     @_fwd32
@@ -231,4 +262,4 @@ class _composite_rays(Function):
 composite_rays = _composite_rays.apply
 
 __all__ = ["near_far_from_aabb", "sph_from_ray", "morton3D", "morton3D_invert", "packbits",
-           "march_rays_train", "composite_rays_train", "march_rays", "composite_rays"]
+           "march_rays_train", "composite_rays_train", "distortion_rays_train", "march_rays", "composite_rays"]
