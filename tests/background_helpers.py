@@ -12,6 +12,7 @@ from PIL import Image
 OFFSETS = [0, 296, 7024, 173488, 697776]
 BASE, LEVELS = 16, 4
 S = float(np.log2(np.exp2(np.log2(2048 / 16) / 3)))  # log2(per_level_scale) of GridEncoder(desired_resolution=2048)
+DEFAULT_S = S
 
 
 def sph64(o, d, radius):
@@ -27,35 +28,60 @@ def sph64(o, d, radius):
     return np.stack([2 * theta / np.pi - 1, phi / np.pi], 1)
 
 
-def grid64(x01, table):
-    """The 2-D hash grid (4 levels x 2 features, bilinear, align_corners off,
-    hash where the dense level would not fit) at x01 [N, 2] in [0, 1], float64
-    interpolation of `table` [entries, 2] -> [N, 8]."""
-    out = np.zeros((x01.shape[0], 2 * LEVELS))
+def grid_levels(offsets=None, base=None, S=None):
+    """Per level (scale, res, off0, hs, dense) of gridencoder's make_levels: scale
+    = exp2f(level * S) * base - 1 in float32, res = ceil(scale) + 1; dense where
+    (res + 1)^2 entries fit in the level's hs."""
+    offsets = OFFSETS if offsets is None else [int(v) for v in offsets]
+    base = BASE if base is None else base
+    S = DEFAULT_S if S is None else S
+    out = []
     for lv in range(LEVELS):
-        scale = np.float32(np.float32(np.exp2(np.float64(np.float32(lv) * np.float32(S)))) * np.float32(BASE)
+        scale = np.float32(np.float32(np.exp2(np.float64(np.float32(lv) * np.float32(S)))) * np.float32(base)
                            - np.float32(1))
         res = int(np.ceil(scale)) + 1
-        off0, hs = OFFSETS[lv], OFFSETS[lv + 1] - OFFSETS[lv]
+        off0, hs = offsets[lv], offsets[lv + 1] - offsets[lv]
+        out.append((scale, res, off0, hs, (res + 1) ** 2 <= hs))
+    return out
+
+
+def grid_corners64(x01, offsets=None, base=None, S=None):
+    """The 2-D hash grid's indexing (4 levels, bilinear, align_corners off, hash
+    where the dense level would not fit) at x01 [N, 2] in [0, 1]: per level
+    (entries [N, 4] int64, rows of the whole table, weights [N, 4] float64)."""
+    x01 = np.asarray(x01, dtype=np.float64)
+    out = []
+    for scale, res, off0, hs, dense in grid_levels(offsets, base, S):
         pos = x01 * np.float64(scale) + 0.5
         pg = np.floor(pos).astype(np.int64)
         fr = pos - pg
+        e = np.zeros((x01.shape[0], 4), dtype=np.int64)
+        w = np.ones((x01.shape[0], 4))
         for idx in range(4):
-            w = np.ones(x01.shape[0])
             pl = np.zeros_like(pg)
             for dd in range(2):
                 if idx & (1 << dd):
-                    w = w * fr[:, dd]
+                    w[:, idx] *= fr[:, dd]
                     pl[:, dd] = pg[:, dd] + 1
                 else:
-                    w = w * (1 - fr[:, dd])
+                    w[:, idx] *= 1 - fr[:, dd]
                     pl[:, dd] = pg[:, dd]
-            if (res + 1) ** 2 <= hs:  # dense: stride res + 1
+            if dense:  # stride res + 1
                 index = pl[:, 0] + pl[:, 1] * (res + 1)
             else:  # fast_hash, primes 1 and 2654435761, in uint32
                 index = ((pl[:, 0] & 0xffffffff) ^ ((pl[:, 1] * 2654435761) & 0xffffffff)) & 0xffffffff
-            e = off0 + index % hs
-            out[:, 2 * lv:2 * lv + 2] += w[:, None] * table[e]
+            e[:, idx] = off0 + index % hs
+        out.append((e, w))
+    return out
+
+
+def grid64(x01, table, offsets=None, base=None, S=None):
+    """Float64 interpolation of `table` [entries, 2] at x01 [N, 2] in [0, 1],
+    through grid_corners64 -> [N, 8]."""
+    out = np.zeros((x01.shape[0], 2 * LEVELS))
+    for lv, (e, w) in enumerate(grid_corners64(x01, offsets, base, S)):
+        for idx in range(4):
+            out[:, 2 * lv:2 * lv + 2] += w[:, idx, None] * table[e[:, idx]]
     return out
 
 
@@ -73,15 +99,109 @@ def sh4(d):
         1.4453057213202769 * z * (x2 - y2), 0.59004358992664352 * x * (-x2 + 3.0 * y2)], 1)
 
 
-def background64(o, d, radius, table_half, weights_half):
-    """The model in float64 on the fp16-rounded table and weights (float64
-    copies of the half values): what every fp16 path approximates. -> [N, 3]."""
+def features64(o, d, radius, table_half, offsets=None, base=None, S=None):
+    """The MLP's input row in float64: [SH4(d) | grid(sph01) | 0 (8)] -> [N, 32]."""
     x01 = (sph64(o, d, radius) + 1) / 2
-    feat = np.concatenate([sh4(d), grid64(x01, table_half.astype(np.float64)), np.zeros((o.shape[0], 8))], 1)
-    w = weights_half.astype(np.float64)
-    w0, w1 = w[:64 * 32].reshape(64, 32), w[64 * 32:].reshape(16, 64)
+    grid = grid64(x01, table_half.astype(np.float64), offsets, base, S)
+    return np.concatenate([sh4(d), grid, np.zeros((o.shape[0], 8))], 1)
+
+
+def split_weights(weights_half):
+    """The flat weights -> W0 [64, 32], W1 [16, 64] in float64."""
+    w = np.asarray(weights_half).astype(np.float64)
+    return w[:64 * 32].reshape(64, 32), w[64 * 32:].reshape(16, 64)
+
+
+def mlp64(feat, weights_half):
+    """sigmoid(W1[:3] relu(W0 x)) in float64 -> [N, 3]."""
+    w0, w1 = split_weights(weights_half)
     h = np.maximum(feat @ w0.T, 0)
     return 1 / (1 + np.exp(-(h @ w1.T)[:, :3]))
+
+
+def background64(o, d, radius, table_half, weights_half, offsets=None, base=None, S=None):
+    """The model in float64 on the fp16-rounded table and weights (float64
+    copies of the half values): what every fp16 path approximates. -> [N, 3]."""
+    return mlp64(features64(o, d, radius, table_half, offsets, base, S), weights_half)
+
+
+def uncertain_units(x, weights_half):
+    """[N, 64] bool: hidden units whose float64 pre-activation h = W0 x lies
+    within 64 * 2^-24 * sum |w| |x| of zero, twice the worst-case error of a
+    32-term fp32 dot product: an fp32 evaluation could put the ReLU's mask the
+    other way there."""
+    w0, _ = split_weights(weights_half)
+    x = np.asarray(x).astype(np.float64)
+    return np.abs(x @ w0.T) < 64 * 2.0 ** -24 * (np.abs(x) @ np.abs(w0).T)
+
+
+def bwd_blocks(N):
+    """Workgroups of the backward launch: 256 rays each, at most 64."""
+    return min((N + 255) // 256, 64)
+
+
+def background_backward64(x_half, sph01, bg, out_image, out_ws, gt, weights_half, scale, color_weight, N, offsets=None,
+                          base=None, S=None, order=None, faithful=False):
+    """d (scale * cw * mean((out_image - gt[:, :3])^2)) / d (table, W0, W1[:3]) of
+    the background model in float64, from what the backward reads: the saved
+    input rows x [N, 32], sph01 [N, 2], bg [N, 3], the composite's out_image
+    [N, 3] and out_ws [N], gt [N, 4], the weights:
+        G = scale cw / N / 3,  gy = G 2 (out_image - gt) (1 - out_ws) bg (1 - bg),
+        h = W0 x,  delta = [h > 0] W1[:3]^T gy,  dW1 = gy^T relu(h),  dW0 = delta^T x,
+        gi = W0[:, 16:24]^T delta,  table[e] += w_corner gi[2 l : 2 l + 2]
+    (rays whose sph01 leaves [0, 1] scatter nothing). `order` is the ray-index
+    column of a rays list: one term per entry inside [0, N), none for the rest;
+    None is the identity. -> (g_table [entries, 2], g_w0 [64, 32], g_w1 [3, 64]).
+
+    faithful: gy, relu(h), delta and gi are rounded to fp16 where the kernel
+    rounds them, everything else stays float64; a fourth value is returned, the
+    dict of each output's bound terms: S_* the same expression with every
+    factor's absolute value from gy on, n_table the scatter terms per entry
+    and n_w the workgroups that add to each dW value."""
+    offsets = OFFSETS if offsets is None else [int(v) for v in offsets]
+    idx = np.arange(N) if order is None else np.asarray(order).astype(np.int64).reshape(-1)
+    idx = idx[(idx >= 0) & (idx < N)]
+    f64 = lambda a: np.asarray(a).astype(np.float64)  # noqa: E731
+    r16 = (lambda a: a.astype(np.float16).astype(np.float64)) if faithful else (lambda a: a)
+    x, y, ws = f64(x_half)[idx], f64(bg)[idx], f64(out_ws)[idx]
+    w0, w1 = split_weights(weights_half)
+    w1, w0g = w1[:3], w0[:, 16:24]
+    G = float(scale) * float(color_weight) / N / 3
+    gy = r16(G * 2 * (f64(out_image)[idx] - f64(gt)[idx, :3]) * (1 - ws)[:, None] * (y * (1 - y)))
+    h = x @ w0.T
+    live = h > 0
+    act = r16(np.maximum(h, 0))
+    delta = r16(live * (gy @ w1))
+    gi = r16(delta @ w0g)
+    a_delta = live * (np.abs(gy) @ np.abs(w1))
+    a_gi = a_delta @ np.abs(w0g)
+    g_table, s_table = np.zeros((offsets[-1], 2)), np.zeros((offsets[-1], 2))
+    n_table = np.zeros(offsets[-1], dtype=np.int64)
+    sp = f64(sph01)[idx]
+    inside = ((sp >= 0) & (sp <= 1)).all(1)
+    for lv, (e, w) in enumerate(grid_corners64(sp[inside], offsets, base, S)):
+        for k in range(4):
+            for c in range(2):
+                np.add.at(g_table[:, c], e[:, k], w[:, k] * gi[inside, 2 * lv + c])
+                np.add.at(s_table[:, c], e[:, k], np.abs(w[:, k]) * a_gi[inside, 2 * lv + c])
+            np.add.at(n_table, e[:, k], 1)
+    out = (g_table, delta.T @ x, gy.T @ act)
+    if not faithful:
+        return out
+    return out + (dict(S_table=s_table, S_w0=a_delta.T @ np.abs(x), S_w1=np.abs(gy).T @ act, n_table=n_table,
+                       n_w=bwd_blocks(N)),)
+
+
+def fp16_spacing(a):
+    """The distance between neighbouring fp16 numbers at |a| (2^-24 below 2^-14)."""
+    return np.exp2(np.maximum(np.floor(np.log2(np.maximum(np.abs(a), 2.0 ** -30))), -14.0) - 10)
+
+
+def backward_tolerance(ref, S, n):
+    """4 * 2^-11 * S (three chained fp16 roundings that may fall the other way
+    and the fp32 accumulation) + n * 2^-25 (half a unit of the 2^-24 fixed
+    point per atomic contribution) + the fp16 spacing at |ref| (the final store)."""
+    return 4 * 2.0 ** -11 * S + np.asarray(n, dtype=np.float64) * 2.0 ** -25 + fp16_spacing(ref)
 
 
 def backdrop(d):

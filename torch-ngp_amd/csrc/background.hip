@@ -122,10 +122,18 @@ NGP_DEV void sph01(const float* __restrict__ rays_o, const float* __restrict__ r
 
 // One level's four corners of k_grid_fwd<D = 2> (hash grid, align_corners
 // off, linear): entry indices within the level (always < hs) and weights.
+// kExact = false is the forward's arithmetic, bit for bit: the position
+// x * scale + 0.5 rounded to fp32 before the cell is taken off, so the
+// fraction carries the position's rounding (up to 2^-14 at a scale of 2047).
+// kExact = true (the backward's scatter weights) rounds the fraction itself,
+// frac = fma(x, scale, 0.5 - cell): within 2^-25 of the real one. The rounded
+// position can only reach the next cell's edge from below (an integer is an
+// fp32 number), so a negative fraction means the cell before.
 struct Corners {
     uint32_t e[4];
     float w[4];
 };
+template <bool kExact>
 NGP_DEV Corners level_corners(const float (&x)[2], float scale, uint32_t res, uint32_t hs) {
     const uint32_t hs_mask = (hs & (hs - 1)) == 0 ? hs - 1 : 0;
     float pos[2];
@@ -134,7 +142,15 @@ NGP_DEV Corners level_corners(const float (&x)[2], float scale, uint32_t res, ui
     for (int d = 0; d < 2; ++d) {
         pos[d] = fmaf(x[d], scale, 0.5f);
         pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
+        if (kExact) {
+            pos[d] = fmaf(x[d], scale, 0.5f - (float)pg[d]);
+            if (pos[d] < 0.0f && pg[d] > 0) {
+                pg[d] -= 1;
+                pos[d] = fmaf(x[d], scale, 0.5f - (float)pg[d]);
+            }
+        } else {
+            pos[d] -= (float)pg[d];
+        }
     }
     Corners c;
 #pragma unroll
@@ -185,7 +201,7 @@ NGP_DEV void input_row(const float (&x)[2], const float (&d)[3], const E* __rest
         ngp_half r0 = (ngp_half)0.0f, r1 = (ngp_half)0.0f;
         if (!oob) {
             const uint32_t off0 = offsets.v[l], hs = offsets.v[l + 1] - off0;
-            const Corners c = level_corners(x, lv.scale[l], lv.res[l], hs);
+            const Corners c = level_corners<false>(x, lv.scale[l], lv.res[l], hs);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 struct alignas(sizeof(E) * 2) V { E v[2]; };
@@ -430,6 +446,7 @@ k_bg_backward(const int32_t* __restrict__ rays, uint32_t N, const float* __restr
         }
         // the ray's grid-feature gradient W0[:, 16..24)^T delta, rounded to half
         // (the MLP's fp16 input gradient), scattered with the bilinear weights
+        // (level_corners<true>: the fraction rounded once, not the position)
         if (valid) {
             float gi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll 4
@@ -443,7 +460,7 @@ k_bg_backward(const int32_t* __restrict__ rays, uint32_t N, const float* __restr
 #pragma unroll
                 for (uint32_t l = 0; l < kLevels; ++l) {
                     const uint32_t off0 = lo.v[l], hs = lo.v[l + 1] - off0;
-                    const Corners cn = level_corners(x, lv.scale[l], lv.res[l], hs);
+                    const Corners cn = level_corners<true>(x, lv.scale[l], lv.res[l], hs);
                     const float ga = (float)(ngp_half)gi[2 * l], gb = (float)(ngp_half)gi[2 * l + 1];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
