@@ -1175,6 +1175,34 @@ int ngp_frame_finish(uint32_t H, uint32_t W, const float* image, const float* we
  * bad source, H * W outside [1, 2^28), misalignment: NGP_ERR_ARG. */
 int ngp_frame_sse(uint32_t H, uint32_t W, const float* image, const float* weights_sum, float bg_color,
                   const ngp_image_source* src, uint32_t pose_index, double* sse_out, void* stream);
+/* SSIM beside the squared error: one launch on the same inputs,
+ * x = ngp_frame_sse's c and y = its gt, both float32. Wang et al. 2004 with
+ * the 11 x 11 Gaussian window, sigma 1.5, g[k] = exp(-(k - 5)^2 / (2 * 1.5^2))
+ * normalised to sum 1 (computed here in double and handed to the kernel),
+ * applied separably over the valid region: (H - 10) x (W - 10) positions per
+ * channel, no padding. Per channel and position, with E[.] the windowed mean,
+ *   mux = E[x], muy = E[y], sx = E[x x] - mux mux, sy = E[y y] - muy muy,
+ *   sxy = E[x y] - mux muy,
+ *   ssim = ((2 mux muy + C1) (2 sxy + C2)) / ((mux mux + muy muy + C1) (sx + sy + C2)),
+ *   C1 = 0.01^2, C2 = 0.03^2 (data range 1),
+ * every operation from the float32 x and y on in double without contraction.
+ * ssim_sum_out[pose_index] = the sum of the map's 3 (H - 10) (W - 10) values
+ * (the caller divides for the mean); no other element is written. map_out
+ * (nullable) [(H - 10) * (W - 10) * 3], row-major, channel last: the map; null:
+ * it is never stored. The sum is deterministic in ngp_frame_sse's manner: a
+ * workgroup owns tiles of 32 x 16 positions in a fixed assignment, its threads
+ * add their values in a fixed order and tree, and the workgroup that finishes
+ * last (an integer ticket) adds the partials in index order; no floating-point
+ * atomics, the same bits from run to run for one (H, W). A non-finite x or y
+ * makes the sum non-finite. Nothing outside the H x W images is read. The
+ * partials and the ticket are the library's: one call at a time per device;
+ * the entry clears the ticket on the stream before the launch. The caller
+ * guarantees pose_index < n. Null image / weights_sum / ssim_sum_out, a bad
+ * source, H * W outside [1, 2^28), H or W below 11, image or weights_sum not
+ * 16-byte aligned, ssim_sum_out or map_out not 8-byte aligned: NGP_ERR_ARG. */
+int ngp_frame_ssim(uint32_t H, uint32_t W, const float* image, const float* weights_sum, float bg_color,
+                   const ngp_image_source* src, uint32_t pose_index, double* ssim_sum_out, double* map_out,
+                   void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Background model (the reference's --bg_radius, nerf/network.py:107-129,  */

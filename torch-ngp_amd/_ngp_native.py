@@ -206,6 +206,7 @@ SIGNATURES = {
                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_frame_finish": [c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_frame_sse": [c_u32, c_u32, c_vp, c_vp, c_f32, c_vp, c_u32, c_vp, c_vp],
+    "ngp_frame_ssim": [c_u32, c_u32, c_vp, c_vp, c_f32, c_vp, c_u32, c_vp, c_vp, c_vp],
     "ngp_ema_update": [c_vp, c_vp, ctypes.c_uint64, c_f32, c_vp],
     "ngp_background_scratch_bytes": [ctypes.c_uint64],
     "ngp_background_forward": [c_vp, c_vp, c_f32, c_u32, c_vp, c_i32, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp, c_u32,

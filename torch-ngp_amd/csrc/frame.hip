@@ -13,12 +13,14 @@
 //   k_frame_sse     or, in its place, the validation pass: the blended colour
 //                   against the view's ground-truth image, the squared error
 //                   summed in double on the device
+//   k_frame_ssim    beside it, on the same two images: their SSIM, the 11 x 11
+//                   Gaussian window in double through LDS tiles
 //
-// All make one pass over the pixels and are bound by memory. A thread owns 4
-// consecutive pixels, so every [N] array moves as one 16-byte access per
-// thread, every [N, 3] array as three, the 12 colour bytes as three dwords and
-// the 4 depth bytes as one. The last N % 4 pixels of a frame go element by
-// element (one thread).
+// All but the last make one pass over the pixels and are bound by memory. A
+// thread owns 4 consecutive pixels, so every [N] array moves as one 16-byte
+// access per thread, every [N, 3] array as three, the 12 colour bytes as three
+// dwords and the 4 depth bytes as one. The last N % 4 pixels of a frame go
+// element by element (one thread).
 #include "ngp_common.h"
 #include "ngp_head.h"
 #include "ngp_render.h"
@@ -270,6 +272,126 @@ k_frame_sse(uint32_t N, const float* __restrict__ image, const float* __restrict
     if (threadIdx.x == 0) *sse_out = s_sum[0];
 }
 
+// SSIM of a rendered view against its ground-truth image: the
+// 11 x 11 Gaussian window (sigma 1.5) of Wang et al. 2004 applied separably
+// over the valid region, (H - 10) x (W - 10) positions per channel, on the two
+// float32 images k_frame_sse compares; every operation from those values on is
+// in double (the variances cancel against C2 = 8.1e-4). A workgroup owns tiles
+// of kSsimTileW x kSsimTileH positions: it stages a tile's pixels and the
+// 10-pixel halo of both images (blend and decode done here, zeros past the
+// image), then per channel runs the horizontal pass of the five moments into
+// LDS and the vertical pass and the formula from there. Thread t owns column
+// t % 32 and rows t / 32 and t / 32 + 8 of a tile and adds its values up in
+// tile, channel, row order; workgroups take tiles b, b + gridDim.x, ...; the
+// sum over threads and workgroups is k_frame_sse's (tree, ticket, partials in
+// index order), so it depends on (H, W) alone.
+constexpr uint32_t kSsimWin = 11, kSsimHalo = kSsimWin - 1;
+constexpr uint32_t kSsimTileW = 32, kSsimTileH = 16;
+constexpr uint32_t kSsimInW = kSsimTileW + kSsimHalo, kSsimInH = kSsimTileH + kSsimHalo;  // 42 x 26 staged pixels
+constexpr uint32_t kSsimMaxBlocks = 1024;
+static_assert(kSsimTileW * kSsimTileH == 2 * kThreads, "a thread owns two positions of a tile");
+__device__ double g_ssim_partial[kSsimMaxBlocks];
+__device__ uint32_t g_ssim_ticket;
+
+struct SsimWindow {
+    double g[kSsimWin];  // the normalised 1-D weights, the host's
+};
+
+__global__ void __launch_bounds__(kThreads)
+k_frame_ssim(uint32_t H, uint32_t W, const float* __restrict__ image, const float* __restrict__ weights_sum, float bg,
+             GroundTruth gt, SsimWindow win, uint32_t tiles_x, uint32_t n_tiles, double* __restrict__ map_out,
+             double* __restrict__ ssim_out) {
+    __shared__ float s_in[2][3][kSsimInH][kSsimInW];         // [x | y][channel]: 26,208 bytes
+    __shared__ double s_h[5][kSsimInH][kSsimTileW];          // one channel's horizontal pass: 33,280 bytes
+    __shared__ double s_sum[kThreads];
+    __shared__ uint32_t s_last;
+    const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
+    const uint32_t oh = H - kSsimHalo, ow = W - kSsimHalo;   // the map's extent
+    const uint32_t tc = threadIdx.x % kSsimTileW, tr = threadIdx.x / kSsimTileW;
+    double acc = 0.0;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t y0 = tile / tiles_x * kSsimTileH, x0 = tile % tiles_x * kSsimTileW;
+        for (uint32_t i = threadIdx.x; i < kSsimInH * kSsimInW; i += kThreads) {
+            const uint32_t r = i / kSsimInW, c = i % kSsimInW;
+            float xv[3] = {0.0f, 0.0f, 0.0f}, yv[3] = {0.0f, 0.0f, 0.0f};
+            if (y0 + r < H && x0 + c < W) {  // (only the last tile row / column's positions past the map need the rest)
+                const uint32_t p = (y0 + r) * W + (x0 + c);
+                const float w = (1.0f - weights_sum[p]) * bg;  // k_frame_finish's blend
+#pragma unroll
+                for (int j = 0; j < 3; ++j) xv[j] = image[(size_t)p * 3 + j] + w;
+                ground_truth(gt, p, yv);
+            }
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                s_in[0][j][r][c] = xv[j];
+                s_in[1][j][r][c] = yv[j];
+            }
+        }
+        __syncthreads();
+        for (uint32_t ch = 0; ch < 3; ++ch) {
+            for (uint32_t i = threadIdx.x; i < kSsimInH * kSsimTileW; i += kThreads) {
+                const uint32_t r = i / kSsimTileW, c = i % kSsimTileW;
+                double m[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (uint32_t k = 0; k < kSsimWin; ++k) {
+                    const double x = (double)s_in[0][ch][r][c + k], y = (double)s_in[1][ch][r][c + k], g = win.g[k];
+                    m[0] += g * x;
+                    m[1] += g * y;
+                    m[2] += g * (x * x);
+                    m[3] += g * (y * y);
+                    m[4] += g * (x * y);
+                }
+#pragma unroll
+                for (int q = 0; q < 5; ++q) s_h[q][r][c] = m[q];
+            }
+            __syncthreads();
+#pragma unroll
+            for (uint32_t half = 0; half < 2; ++half) {
+                const uint32_t r = tr + half * (kSsimTileH / 2);
+                double m[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (uint32_t k = 0; k < kSsimWin; ++k)
+#pragma unroll
+                    for (int q = 0; q < 5; ++q) m[q] += win.g[k] * s_h[q][r + k][tc];
+                const double mux = m[0], muy = m[1];
+                const double sx = m[2] - mux * mux, sy = m[3] - muy * muy, sxy = m[4] - mux * muy;
+                const double v = ((2.0 * mux * muy + C1) * (2.0 * sxy + C2)) /
+                                 ((mux * mux + muy * muy + C1) * (sx + sy + C2));
+                if (y0 + r < oh && x0 + tc < ow) {
+                    acc += v;
+                    if (map_out) map_out[((size_t)(y0 + r) * ow + (x0 + tc)) * 3 + ch] = v;
+                }
+            }
+            __syncthreads();  // s_h, and after the last channel s_in, are written again
+        }
+    }
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t o = kThreads / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(&g_ssim_partial[blockIdx.x], s_sum[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        s_last = atomicAdd(&g_ssim_ticket, 1u) == gridDim.x - 1u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    // the last workgroup: partial b to thread b % 256 in ascending b, then the same tree
+    acc = 0.0;
+    for (uint32_t b = threadIdx.x; b < gridDim.x; b += kThreads)
+        acc += __hip_atomic_load(&g_ssim_partial[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (uint32_t o = kThreads / 2; o > 0; o >>= 1) {
+        if (threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *ssim_out = s_sum[0];
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int check_frame_size(uint32_t H, uint32_t W, const char* who) {
@@ -344,4 +466,42 @@ extern "C" int ngp_frame_sse(uint32_t H, uint32_t W, const float* image, const f
     k_frame_sse<<<blocks, kThreads, 0, ngp_stream(stream)>>>(N, image, weights_sum, bg_color, gt,
                                                              sse_out + pose_index);
     return ngp_check_launch("frame_sse");
+}
+
+extern "C" int ngp_frame_ssim(uint32_t H, uint32_t W, const float* image, const float* weights_sum, float bg_color,
+                              const ngp_image_source* src, uint32_t pose_index, double* ssim_sum_out,
+                              double* map_out, void* stream) {
+    if (int e = check_frame_size(H, W, "frame_ssim")) return e;
+    if (int e = ngp_head::check_image_source(src, "frame_ssim")) return e;
+    NGP_REQUIRE(image && weights_sum && ssim_sum_out, NGP_ERR_ARG, "frame_ssim: null buffer");
+    NGP_REQUIRE(aligned16(image) && aligned16(weights_sum) &&
+                    (reinterpret_cast<uintptr_t>(ssim_sum_out) & 7u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(map_out) & 7u) == 0,
+                NGP_ERR_ARG, "frame_ssim: float buffers must be 16-byte aligned, ssim_sum_out and map_out 8-byte aligned");
+    NGP_REQUIRE(H >= kSsimWin && W >= kSsimWin, NGP_ERR_ARG,
+                "frame_ssim: the 11 x 11 window needs H, W >= 11, got %u x %u", H, W);
+    const uint32_t N = H * W;
+    const size_t px_bytes = (size_t)src->channels * (src->dtype == NGP_DTYPE_F32 ? 4 : 1);
+    const GroundTruth gt{static_cast<const char*>(src->pixels) + (size_t)pose_index * N * px_bytes, src->channels,
+                         src->dtype};
+    // g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), normalised to sum 1 (added in ascending k)
+    SsimWindow win;
+    double total = 0.0;
+    for (uint32_t k = 0; k < kSsimWin; ++k) {
+        const double d = (double)k - 5.0;
+        win.g[k] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
+        total += win.g[k];
+    }
+    for (uint32_t k = 0; k < kSsimWin; ++k) win.g[k] /= total;
+    const uint32_t tiles_x = ngp_div_up(W - kSsimHalo, kSsimTileW), tiles_y = ngp_div_up(H - kSsimHalo, kSsimTileH);
+    const uint32_t n_tiles = tiles_x * tiles_y;
+    const uint32_t blocks = n_tiles < kSsimMaxBlocks ? n_tiles : kSsimMaxBlocks;  // a function of (H, W) alone
+    // the ticket starts at 0 whatever an earlier pass left (one that was aborted, say)
+    void* ticket = nullptr;
+    NGP_REQUIRE(hipGetSymbolAddress(&ticket, HIP_SYMBOL(g_ssim_ticket)) == hipSuccess &&
+                    hipMemsetAsync(ticket, 0, sizeof(uint32_t), ngp_stream(stream)) == hipSuccess,
+                NGP_ERR_HIP, "frame_ssim: could not clear the ticket");
+    k_frame_ssim<<<blocks, kThreads, 0, ngp_stream(stream)>>>(H, W, image, weights_sum, bg_color, gt, win, tiles_x,
+                                                              n_tiles, map_out, ssim_sum_out + pose_index);
+    return ngp_check_launch("frame_ssim");
 }

@@ -40,7 +40,9 @@ validates on the device every E epochs (nerf.eval.Validator over the val
 split) and keeps the best model in <workspace>/checkpoints/ngp_best.pth
 (--test --ckpt best renders it). --resume continues from
 <workspace>/checkpoints/ngp.pth (or --ckpt PATH) to --iters. DESIGN.md
-section 16.
+section 16. --ssim reports SSIM beside every PSNR (the periodic validation,
+the final evaluation, and under --test the test split's own views), computed
+on the device beside the squared error.
 
 Not here: patch sampling, --color_space linear, more than one
 image per batch, video files."""
@@ -102,6 +104,9 @@ def get_parser():
     p.add_argument("--eval_interval", type=int, default=0,
                    help="validate every this many epochs (an epoch is one step per training view) and keep the best "
                         "model in <workspace>/checkpoints/ngp_best.pth; 0: evaluate only at the end")
+    p.add_argument("--ssim", action="store_true",
+                   help="report SSIM (11 x 11 Gaussian window, sigma 1.5, valid region) beside PSNR, computed on the "
+                        "device; the best checkpoint stays chosen by PSNR")
     p.add_argument("--resume", action="store_true",
                    help="continue training from <workspace>/checkpoints/ngp.pth (or --ckpt PATH) up to --iters")
     # test mode (the reference's --test / --ckpt and its trainer.test, main_nerf.py:188 / :239)
@@ -125,8 +130,9 @@ def _eval_split(path):
 
 def _test_path(opt, train, dev, data_args):
     """The cameras of the test frames -> (poses [n, 4, 4], H, W, intrinsics,
-    what they are): the test split's, or the reference's interpolation
-    (provider.py:208-222) between two training poses drawn with --seed."""
+    what they are, the test split's dataset or None): the test split's, or the
+    reference's interpolation (provider.py:208-222) between two training poses
+    drawn with --seed."""
     import numpy as np
 
     from nerf.provider import NeRFDataset, interpolate_poses
@@ -134,7 +140,7 @@ def _test_path(opt, train, dev, data_args):
     if not os.path.exists(os.path.join(opt.path, "transforms.json")) and \
             os.path.exists(os.path.join(opt.path, "transforms_test.json")):
         test = NeRFDataset(opt.path, dev, type="test", num_rays=opt.num_rays, **data_args)
-        return test.poses, test.H, test.W, test.intrinsics, "test poses"
+        return test.poses, test.H, test.W, test.intrinsics, "test poses", test
     if train is None:  # --test: only the interpolated path needs the training views
         train = NeRFDataset(opt.path, dev, type="train", num_rays=opt.num_rays, **data_args)
     n = int(train.poses.shape[0])
@@ -143,7 +149,7 @@ def _test_path(opt, train, dev, data_args):
                  f"(the scene has {n}) and --test_frames >= 1 (got {opt.test_frames})")
     a, b = np.random.default_rng(opt.seed).choice(n, 2, replace=False)
     poses = interpolate_poses(train.poses[a].cpu().numpy(), train.poses[b].cpu().numpy(), opt.test_frames)
-    return poses, train.H, train.W, train.intrinsics, f"poses between training views {a} and {b}"
+    return poses, train.H, train.W, train.intrinsics, f"poses between training views {a} and {b}", None
 
 
 def _ckpt_path(opt):
@@ -151,14 +157,25 @@ def _ckpt_path(opt):
     return os.path.join(opt.workspace, "checkpoints", name) if name else opt.ckpt
 
 
-def _write_test_frames(opt, model, train, dev, data_args, source=None):
+def _ssim_validator(opt, model, data):
+    """Validator(ssim=True) over `data`; a frame smaller than the window ends the run."""
+    from nerf.eval import Validator
+    try:
+        return Validator(model, data, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma, ssim=True)
+    except ValueError as e:
+        sys.exit(f"[main_nerf] --ssim: {e}")
+
+
+def _write_test_frames(opt, model, train, dev, data_args, source=None, evaluate=False):
     """trainer.test (nerf/utils.py:743-796): every test pose rendered in eval
     mode on a white background, written under <workspace>/results. source: the
-    weights to render instead of the model's own (the EMA's)."""
+    weights to render instead of the model's own (the EMA's). evaluate (--test
+    --ssim): the reference's trainer.evaluate(test_loader) where the frames are
+    a split with images: its PSNR and SSIM, printed and added to the result."""
     import torch
 
     from nerf.frames import FrameRenderer, write_frames
-    poses, H, W, intrinsics, what = _test_path(opt, train, dev, data_args)
+    poses, H, W, intrinsics, what, test = _test_path(opt, train, dev, data_args)
     was_training = model.training
     model.eval()
     fr = FrameRenderer(model, H, W, intrinsics, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma, bg_color=1.0)
@@ -173,7 +190,15 @@ def _write_test_frames(opt, model, train, dev, data_args, source=None):
     model.train(was_training)
     print(f"[main_nerf] {len(fr)} frames {H}x{W} ({what}) in {secs:.2f} s, {len(fr) / secs:.1f} frames/s, "
           f"written to {out_dir}")
-    return {"frames": len(fr), "frames_per_second": len(fr) / secs, "results": out_dir, "frame_paths": paths}
+    result = {"frames": len(fr), "frames_per_second": len(fr) / secs, "results": out_dir, "frame_paths": paths}
+    if evaluate and (test is None or getattr(test, "images", None) is None):
+        print("[main_nerf] --ssim: the test frames have no images to compare with (an interpolated camera path)")
+    elif evaluate:
+        res = _ssim_validator(opt, model, test).run(source=source)
+        print(f"[main_nerf] PSNR {res['mean_psnr']:.4f} over {len(res['views'])} test images")
+        print(f"[main_nerf] SSIM {res['mean_ssim']:.4f} over {len(res['views'])} test images")
+        result.update(psnr=res["mean_psnr"], ssim=res["mean_ssim"])
+    return result
 
 
 def _test(opt, dev, bound, data_args):
@@ -200,7 +225,7 @@ def _test(opt, dev, bound, data_args):
     print(f"[main_nerf] checkpoint {ckpt} (step {state.get('global_step', '?')}"
           + (", EMA weights" if source is not None else "") + ")")
     result = {"checkpoint": ckpt}
-    result.update(_write_test_frames(opt, model, None, dev, data_args, source))
+    result.update(_write_test_frames(opt, model, None, dev, data_args, source, evaluate=opt.ssim))
     if opt.save_mesh:
         path = os.path.join(opt.workspace, "meshes", "ngp.ply")
         nv, nt = mesh.save_mesh(model, path, resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)
@@ -288,11 +313,12 @@ def main(argv=None):
     val, validator, ckpt_dir = None, None, os.path.join(opt.workspace, "checkpoints")
     if stats is None:
         stats = {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None}
-    valid_psnr, best_ckpt = [], None
+    valid_psnr, valid_ssim, best_ckpt = [], [], None
     if opt.eval_interval > 0:
         val = train if split == "train" else NeRFDataset(opt.path, dev, type=split, num_rays=opt.num_rays,
                                                          **data_args)
-        validator = Validator(model, val, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma)
+        validator = _ssim_validator(opt, model, val) if opt.ssim else \
+            Validator(model, val, max_steps=opt.max_steps, dt_gamma=opt.dt_gamma)
 
     def advance(k):
         nonlocal captured
@@ -315,10 +341,13 @@ def main(argv=None):
         tv = time.perf_counter()
         res = validator.run(source=ft.ema_params() if ema else None)
         tv = time.perf_counter() - tv
-        print(f"[main_nerf] epoch {epoch} validation PSNR {res['mean_psnr']:.4f} over {len(res['views'])} {split} "
+        print(f"[main_nerf] epoch {epoch} validation PSNR {res['mean_psnr']:.4f}"
+              + (f" SSIM {res['mean_ssim']:.4f}" if opt.ssim else "") + f" over {len(res['views'])} {split} "
               f"images ({tv:.3f} s)")
         stats["valid_loss"].append(res["mean_mse"])
         valid_psnr.append(res["mean_psnr"])
+        if opt.ssim:
+            valid_ssim.append(res["mean_ssim"])
         if stats["best_result"] is None or res["mean_psnr"] > stats["best_result"]:
             stats["best_result"] = res["mean_psnr"]
             best = ft.checkpoint(full=False, epoch=epoch, stats=stats)
@@ -385,6 +414,12 @@ def main(argv=None):
     finite = [s for s in scores if math.isfinite(s)]
     mean_psnr = sum(finite) / len(finite) if finite else float("inf")
     print(f"[main_nerf] PSNR {mean_psnr:.4f} over {len(scores)} {split} images")
+    # ... and, with --ssim, a device pass over the same views with the same weights
+    mean_ssim = None
+    if opt.ssim:
+        res = (validator if validator is not None else _ssim_validator(opt, model, val)).run(source=source)
+        mean_ssim = res["mean_ssim"]
+        print(f"[main_nerf] SSIM {mean_ssim:.4f} over {len(res['views'])} {split} images")
     # ... and the supervised depth term over the same views, when the split has depth maps
     mean_depth = None
     if val.depths is not None:
@@ -412,6 +447,8 @@ def main(argv=None):
               "seconds": secs, "depth_error": mean_depth, "start_step": start, "epoch": epoch,
               "valid_psnr": valid_psnr, "best_checkpoint": best_ckpt, "dist_loss": ft.last_dist_loss,
               "ray_distortion": mean_dist}
+    if opt.ssim:
+        result.update(ssim=mean_ssim, valid_ssim=valid_ssim)
     if opt.save_mesh:
         ft.workspace = opt.workspace
         path, nv, nt = ft.save_mesh(resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)
