@@ -990,6 +990,12 @@ int ngp_grad_exchange_reduce(const void* recv, int32_t world, uint32_t cap, void
 /* raymarching.h:11)                                                          */
 /* ------------------------------------------------------------------------ */
 
+/* Every entry below that takes a grid shape requires 1 <= C <= 16 cascades and
+ * H a power of two in [2, 1024] with C * H^3 < 2^32 (a cell's index is
+ * cascade * H^3 + its Morton code, below H^3 only for a power of two), and
+ * returns NGP_ERR_ARG otherwise. The threshold is Python's min(mean_density,
+ * density_thresh): a NaN mean stays NaN and clears every bit. */
+
 /* The query points of one update, P = C * ppc ordered by cascade. coords
  * int32 [P,3] cell coordinates (renderer.py:552-561), or NULL for every cell
  * of each cascade in meshgrid(x, y, z, 'ij') order (ppc = H^3, :516-523);

@@ -182,80 +182,7 @@ def test_mark_untrained_grid_matches_numpy(cuda):
 
 # ---- FusedTrainer.update_density: device-side draws -------------------------------
 
-def _mix32(x):
-    x = np.asarray(x, np.uint32)
-    with np.errstate(over="ignore"):
-        x = x ^ (x >> np.uint32(16)); x = x * np.uint32(0x7feb352d)
-        x = x ^ (x >> np.uint32(15)); x = x * np.uint32(0x846ca68b)
-        x = x ^ (x >> np.uint32(16))
-    return x
-
-
-def _rng_u32(seed, a, b, c):
-    """csrc/density_grid.hip rng_u32 (counter RNG), restated in numpy uint32."""
-    with np.errstate(over="ignore"):
-        inner = _mix32(np.asarray(b, np.uint32) ^ _mix32(np.uint32(c) + np.uint32(0x85ebca6b)))
-        return _mix32(np.uint32(seed) ^ _mix32(np.uint32(a) + np.uint32(0x9e3779b9) * inner))
-
-
-DENSITY_RNG_DOMAIN = 0xd3a5b1c7  # csrc/density_grid.hip kDensityRngDomain
-
-
-def _draws(seed, update, P, ppc, H, grid=None):
-    seed = np.uint32(seed ^ DENSITY_RNG_DOMAIN)
-    p = np.arange(P, dtype=np.uint32)
-    noise = np.stack([(_rng_u32(seed, update, p, 1 + j) >> np.uint32(8)).astype(np.float32) * np.float32(2 ** -24)
-                      for j in range(3)], -1)
-    if grid is None:
-        return None, noise
-    coords = np.stack([_rng_u32(seed, update, p, 8 + j) % np.uint32(H) for j in range(3)], -1).astype(np.int32)
-    cas, k = p // ppc, p % ppc
-    for c in range(grid.shape[0]):
-        occ = np.nonzero(grid[c] > 0)[0].astype(np.int32)
-        sel = (cas == c) & (k >= ppc // 2)
-        if occ.size:
-            cells = occ[_rng_u32(seed, update, p[sel], 7) % np.uint32(occ.size)]
-            coords[sel] = oracle.morton3D_invert(cells)
-    return coords, noise
-
-
-def _exp_fixed(r):
-    """csrc/density_grid.hip exp_fixed: -ln(u) of u = ((r >> 8) + 1) / 2^24 in
-    2^-32 fixed point, the same IEEE double operations in the same order."""
-    v = (np.asarray(r, np.uint32) >> np.uint32(8)).astype(np.uint64) + np.uint64(1)
-    e = np.array([int(x).bit_length() - 1 for x in v.ravel()], np.int64).reshape(v.shape)
-    m = v.astype(np.float64) / np.exp2(e.astype(np.float64))
-    s = (m - 1.0) / (m + 1.0)
-    s2 = s * s
-    q = np.full_like(s, 1.0 / 15.0)
-    for c in (1.0 / 13.0, 1.0 / 11.0, 1.0 / 9.0, 1.0 / 7.0, 1.0 / 5.0, 1.0 / 3.0, 1.0):
-        q = q * s2 + c
-    lnm = 2.0 * s * q
-    E = (24 - e).astype(np.float64) * 0.6931471805599453 - lnm
-    return np.where(E > 0, (np.maximum(E, 0) * 4294967296.0).astype(np.uint64), np.uint64(0))
-
-
-def _draws_ostat(seed, update, C, H, grid):
-    """ngp_density_grid_draw_sorted's draws (cells per point, uniform half then
-    occupied half per cascade) restated in numpy: uniform order statistics
-    S_k / S_N from the prefix sums of N + 1 fixed-point exponentials."""
-    seed = np.uint32(seed ^ DENSITY_RNG_DOMAIN)
-    H3, N = H ** 3, H ** 3 // 4
-    j = np.arange(N + 1, dtype=np.uint32)
-    cells = []
-    for cas in range(C):
-        occ = np.nonzero(grid[cas] > 0)[0].astype(np.int64)
-        for half in range(2):
-            E = _exp_fixed(_rng_u32(seed, update, j, 16 + 2 * cas + half))
-            S = np.cumsum(E, dtype=np.uint64)
-            t = S[:N].astype(np.float64) / np.float64(S[N])
-            if half and occ.size:
-                cells.append(occ[np.minimum(np.floor(t * occ.size), occ.size - 1).astype(np.int64)])
-            else:
-                cells.append(np.minimum(np.floor(t * H3), H3 - 1).astype(np.int64))
-    cells = np.concatenate(cells)
-    _, noise = _draws(int(seed ^ np.uint32(DENSITY_RNG_DOMAIN)), update, C * 2 * N, 2 * N, H)
-    return oracle.morton3D_invert(cells.astype(np.int32)).astype(np.int32), noise, cells
+from density_cases import DENSITY_RNG_DOMAIN, _draws, _draws_ostat, _exp_fixed, _rng_u32  # noqa: E402,F401
 
 
 @torch.no_grad()

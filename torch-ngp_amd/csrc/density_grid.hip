@@ -50,6 +50,14 @@ struct CascadeScales {
     float hgs[kMaxCascades];  // float(bound_c / H): half a cell
 };
 
+// Every entry's grid shape: 1..kMaxCascades cascades of H^3 cells, H a power of
+// two in [2, 1024] (a cell's index is cascade * H^3 + its Morton code, which
+// stays below H^3 only then), the cells of all cascades countable in 32 bits.
+static bool grid_shape_ok(uint32_t C, uint32_t H) {
+    return C >= 1 && C <= kMaxCascades && H >= 2 && H <= 1024 && (H & (H - 1)) == 0 &&
+           (uint64_t)C * H * H * H <= 0xffffffffull;
+}
+
 // Host side of :528-529: bound_c = min(2^c, bound), hgs = bound_c / H in double
 // (Python floats), each rounded to float where torch multiplies by it.
 static CascadeScales cascade_scales(uint32_t C, uint32_t H, float bound) {
@@ -98,19 +106,13 @@ k_density_points(const int32_t* __restrict__ coords, const float* __restrict__ n
         // corners share cache lines in the query's grid forward (row order
         // of the points: meshgrid, as the reference's draws, :521-533, read
         // from the cell's meshgrid row)
-        // (H a power of two, where the Morton codes below H^3 are exactly the
-        // cube's cells; otherwise meshgrid order)
+        // (H is a power of two, the entries' precondition: the Morton codes
+        // below H^3 are exactly the cube's cells)
         const uint32_t i = p - cas * ppc;
-        if ((H & (H - 1)) == 0) {
-            c[0] = compact_bits(i);
-            c[1] = compact_bits(i >> 1);
-            c[2] = compact_bits(i >> 2);
-            q = (size_t)cas * ppc + ((size_t)c[0] * H + c[1]) * H + c[2];
-        } else {
-            c[0] = i / (H * H);
-            c[1] = (i / H) % H;
-            c[2] = i % H;
-        }
+        c[0] = compact_bits(i);
+        c[1] = compact_bits(i >> 1);
+        c[2] = compact_bits(i >> 2);
+        q = (size_t)cas * ppc + ((size_t)c[0] * H + c[1]) * H + c[2];
     }
     // xyzs = 2 * coords.float() / (H - 1) - 1 (tensor / scalar: times the fp32 reciprocal)
     const float inv = 1.0f / (float)(H - 1);
@@ -186,6 +188,8 @@ k_density_ema(float* __restrict__ grid, float* __restrict__ tmp, uint32_t n, flo
 // packbits at thresh = min(mean_density, density_thresh): mean_density is
 // torch.mean(...).item() of the fp32 grid (a float32 value), compared with
 // the Python float density_thresh in double; the winner is cast to float.
+// Python's min(a, b) is "b if b < a else a": a NaN mean stays NaN (no cell is
+// above it, every bit clears) and a NaN density_thresh gives the mean.
 __global__ void __launch_bounds__(256)
 k_density_pack(const float* __restrict__ grid, uint32_t nbytes, uint32_t n, const double* __restrict__ partial,
                uint32_t nparts, double density_thresh, uint8_t* __restrict__ bitfield, double* __restrict__ stats) {
@@ -214,7 +218,7 @@ k_density_pack(const float* __restrict__ grid, uint32_t nbytes, uint32_t n, cons
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nbytes) return;
     const double mean = (double)(float)(sum / (double)n);
-    const float thresh = (float)(mean < density_thresh ? mean : density_thresh);
+    const float thresh = (float)(density_thresh < mean ? density_thresh : mean);
     const float4* g = reinterpret_cast<const float4*>(grid + (size_t)b * 8);
     const float4 a = g[0], c = g[1];
     uint32_t bits = 0;
@@ -698,8 +702,8 @@ extern "C" int ngp_density_grid_points_sorted(const int32_t* coords, const float
                                               void* stream) {
     NGP_REQUIRE(coords && noise && xyzs && indices && ws, NGP_ERR_ARG,
                 "density_grid_points_sorted: null coords / noise / xyzs / indices / workspace");
-    NGP_REQUIRE(C >= 1 && C <= kMaxCascades && H >= 2 && H <= 1024, NGP_ERR_ARG,
-                "density_grid_points_sorted: cascade %u / grid size %u out of range", C, H);
+    NGP_REQUIRE(grid_shape_ok(C, H), NGP_ERR_ARG,
+                "density_grid_points_sorted: cascade %u / grid size %u (a power of two) out of range", C, H);
     NGP_REQUIRE(ppc > 0 && P == ppc * C && lo <= hi && hi <= P, NGP_ERR_ARG,
                 "density_grid_points_sorted: P = %u is not %u points x %u cascades, or [%u, %u) outside it", P, ppc,
                 C, lo, hi);
@@ -725,8 +729,8 @@ extern "C" int ngp_density_grid_points(const int32_t* coords, const float* noise
                                        uint32_t C, uint32_t H, float bound, float* xyzs, int32_t* indices,
                                        void* stream) {
     NGP_REQUIRE(noise && xyzs && indices, NGP_ERR_ARG, "density_grid_points: null noise / xyzs / indices");
-    NGP_REQUIRE(C >= 1 && C <= kMaxCascades && H >= 2 && H <= 1024, NGP_ERR_ARG,
-                "density_grid_points: cascade %u / grid size %u out of range", C, H);
+    NGP_REQUIRE(grid_shape_ok(C, H), NGP_ERR_ARG,
+                "density_grid_points: cascade %u / grid size %u (a power of two) out of range", C, H);
     NGP_REQUIRE(ppc > 0 && P == ppc * C, NGP_ERR_ARG, "density_grid_points: P = %u is not %u points x %u cascades",
                 P, ppc, C);
     NGP_REQUIRE(coords || ppc == H * H * H, NGP_ERR_ARG, "density_grid_points: all-cell mode needs ppc = H^3");
@@ -739,7 +743,8 @@ extern "C" int ngp_density_grid_points(const int32_t* coords, const float* noise
 extern "C" int ngp_density_grid_ema_pack(float* grid, float* tmp_grid, uint32_t C, uint32_t H, float decay,
                                          double density_thresh, double* stats, uint8_t* bitfield, void* stream) {
     NGP_REQUIRE(grid && tmp_grid && stats && bitfield, NGP_ERR_ARG, "density_grid_ema_pack: null pointer");
-    NGP_REQUIRE(H % 2 == 0 && C >= 1, NGP_ERR_ARG, "density_grid_ema_pack: grid size %u must be even", H);
+    NGP_REQUIRE(grid_shape_ok(C, H), NGP_ERR_ARG,
+                "density_grid_ema_pack: cascade %u / grid size %u (a power of two) out of range", C, H);
     const uint32_t n = C * H * H * H;
     hipStream_t st = ngp_stream(stream);
     // stats: [0] the sum, [1..] the EMA blocks' partial sums
@@ -760,7 +765,7 @@ extern "C" int ngp_density_grid_draw_sorted(const float* grid, uint32_t C, uint3
                                             void* ostat_ws, size_t ostat_ws_bytes, float* xyzs, int32_t* indices,
                                             void* stream) {
     NGP_REQUIRE(grid && draw_ws && ostat_ws && xyzs && indices, NGP_ERR_ARG, "density_grid_draw_sorted: null pointer");
-    NGP_REQUIRE(C >= 1 && C <= kMaxCascades && H >= 2 && H <= 1024 && (H & (H - 1)) == 0 && H % 2 == 0, NGP_ERR_ARG,
+    NGP_REQUIRE(grid_shape_ok(C, H), NGP_ERR_ARG,
                 "density_grid_draw_sorted: cascade %u / grid size %u (a power of two) out of range", C, H);
     const uint32_t H3 = H * H * H, N = H3 / 4, P = C * 2 * N;
     NGP_REQUIRE(lo <= hi && hi <= P, NGP_ERR_ARG, "density_grid_draw_sorted: [%u, %u) outside the %u draws", lo, hi,
@@ -790,8 +795,10 @@ extern "C" int ngp_density_grid_draw_sorted(const float* grid, uint32_t C, uint3
 extern "C" int ngp_density_grid_run_max(const float* sigma, const int32_t* indices, uint32_t C, uint32_t H,
                                         uint32_t lo, uint32_t hi, float* tmp_grid, void* stream) {
     NGP_REQUIRE(sigma && indices && tmp_grid, NGP_ERR_ARG, "density_grid_run_max: null pointer");
+    NGP_REQUIRE(grid_shape_ok(C, H), NGP_ERR_ARG,
+                "density_grid_run_max: cascade %u / grid size %u (a power of two) out of range", C, H);
     const uint32_t N = H * H * H / 4;
-    NGP_REQUIRE(N > 0 && lo <= hi && hi <= C * 2 * N, NGP_ERR_ARG, "density_grid_run_max: bad range");
+    NGP_REQUIRE(lo <= hi && hi <= C * 2 * N, NGP_ERR_ARG, "density_grid_run_max: bad range");
     if (hi == lo) return NGP_OK;
     hipStream_t st = ngp_stream(stream);
     k_density_run_max<<<ngp_div_up(hi - lo, 256), 256, 0, st>>>(sigma, indices, lo, hi, N, tmp_grid);
@@ -807,6 +814,8 @@ extern "C" int ngp_density_grid_draw(const float* grid, uint32_t C, uint32_t H, 
                                      uint32_t update, int32_t* coords, float* noise, void* ws, size_t ws_bytes,
                                      void* stream) {
     NGP_REQUIRE(noise && (!partial || (coords && grid && ws)), NGP_ERR_ARG, "density_grid_draw: null pointer");
+    NGP_REQUIRE(grid_shape_ok(C, H), NGP_ERR_ARG,
+                "density_grid_draw: cascade %u / grid size %u (a power of two) out of range", C, H);
     NGP_REQUIRE(!partial || ws_bytes >= ngp_density_grid_draw_workspace_bytes(C, H), NGP_ERR_ARG,
                 "density_grid_draw: workspace too small");
     const uint32_t H3 = H * H * H;

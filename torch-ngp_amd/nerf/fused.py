@@ -671,7 +671,7 @@ class FusedTrainer:
         P = C * ppc
         lo, hi = self.rank * P // self.world, (self.rank + 1) * P // self.world
         lo0, e, n = lo, self.enc, hi - lo
-        sorted_ = bool(partial and self._dens_sorted and H & (H - 1) == 0)
+        sorted_ = bool(partial and self._dens_sorted)
         if sorted_:
             # this rank's slice of the draws, generated in Morton order (the
             # same i.i.d. draws as order statistics), at the head of xyzs / idx
@@ -714,7 +714,7 @@ class FusedTrainer:
             nat.check(lib.ngp_nerf_density_forward(P_(d["enc"]), P_(self.w_half[1]), P_(self.mlp_img[0]), n,
                                                    sn.input_dim, sn.hidden_dim, sn.num_layers, float(m.density_scale),
                                                    P_(d["idx"]), P_(d["tmp"]), s), "nerf_density_forward")
-        elif not partial and H & (H - 1) == 0:
+        elif not partial:
             # the full update's point p is cell p (Morton order): densities straight into tmp_grid
             nat.check(lib.ngp_nerf_density_forward_rows(*dens, P_(d["tmp"]) + 4 * lo, s), "nerf_density_forward_rows")
         else:

@@ -50,6 +50,9 @@ class NeRFRenderer(nn.Module):
         super().__init__()
         self.bound = bound
         self.cascade = 1 + math.ceil(math.log2(bound))
+        # a cell's index is its Morton code: below grid_size^3 only for a power of two
+        if not (isinstance(grid_size, int) and 2 <= grid_size <= 1024 and grid_size & (grid_size - 1) == 0):
+            raise ValueError(f"grid_size must be a power of two in [2, 1024], got {grid_size!r}")
         self.grid_size = grid_size
         self.density_scale = density_scale
         self.min_near = min_near
