@@ -1265,6 +1265,55 @@ int ngp_background_backward(const int32_t* rays, uint32_t N, const float* out_im
                             uint32_t num_layers, const void* state, float color_weight, float radius, void* scratch,
                             void* grad_table, void* grad_weights, int32_t* inf_flag, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Baseline JPEG of a uint8 frame on the device: csrc/jpeg.hip, DESIGN.md 19 */
+/* ------------------------------------------------------------------------ */
+
+/* The worst-case size in bytes of the entropy-coded scan ngp_jpeg_encode writes
+ * for an H x W image of `components` (1 or 3) components: with B = ceil(W / 8)
+ * * components blocks in each of the n = ceil(H / 8) restart intervals,
+ * n * (2 * (216 * B + 1) + 2). Every coefficient costs at most a 16-bit code and
+ * 11 magnitude bits (a ZRL is charged to the first of its 16 zeros, the EOB to
+ * the first trailing zero), so a block is at most 64 * 27 bits = 216 bytes; the
+ * padding completes at most one more byte per interval, byte stuffing at most
+ * doubles the bytes, and each interval but the last is followed by the 2 bytes
+ * of RSTm. 0 for components outside {1, 3} or H, W outside [1, 65535]. */
+size_t ngp_jpeg_scan_capacity(uint32_t H, uint32_t W, uint32_t components);
+/* int16 elements of ngp_jpeg_encode's workspace: the [blocks, 64] coefficients,
+ * then the library's own part (the intervals' lengths and their byte-stuffed
+ * slabs of 2 * (216 * B + 1) bytes each). 0 for the arguments above. */
+size_t ngp_jpeg_workspace_elems(uint32_t H, uint32_t W, uint32_t components);
+/* Baseline sequential JPEG (T.81 SOF0, 8 bit) of pixels u8 [H, W, 3] (RGB) or
+ * [H, W] (components 3 / 1) on the device: the entropy-coded scan, i.e. the
+ * bytes between the SOS header and EOI, into out; *out_len (device) = its
+ * length. Three launches on `stream`, no host synchronisation, no
+ * floating-point atomics; the bytes depend on the inputs alone.
+ *   - 3 components: Y, Cb, Cr by the JFIF conversion in fp32 (Y = 0.299 R +
+ *     0.587 G + 0.114 B, Cb = -0.168736 R - 0.331264 G + 0.5 B + 128, Cr = 0.5 R -
+ *     0.418688 G - 0.081312 B + 128, no rounding in between), all sampled 1 x 1;
+ *     the MCU is one 8 x 8 block per component, Y, Cb, Cr. Level shift -128.
+ *     Edge blocks repeat the last column and row.
+ *   - 8 x 8 DCT-II in fp32, orthonormal (T.81 A.3.3); each coefficient divided
+ *     by its quantiser (qtable_luma / qtable_chroma: HOST arrays of 64 values in
+ *     natural order, each in 1..255; qtable_chroma may be null for 1 component)
+ *     and rounded to nearest (a tie may go either way); DC clamped to +-2047, AC
+ *     to +-1023; zigzag order of T.81 Figure A.6.
+ *   - coef_ws: int16 [ngp_jpeg_workspace_elems], 16-byte aligned; its first
+ *     blocks * 64 elements receive the quantised coefficients in zigzag order,
+ *     block (mcu_row * ceil(W / 8) + mcu_col) * components + component.
+ *   - Huffman coding with the typical tables of T.81 Annex K.3 (csrc/
+ *     jpeg_tables.h). Restart interval = one MCU row (DRI = ceil(W / 8)): DC
+ *     predictors reset, the last byte padded with 1 bits, RSTm (m = interval mod
+ *     8) after every interval but the last, 0xFF followed by 0x00 inside.
+ * capacity: the bytes of out, at least ngp_jpeg_scan_capacity (bytes past
+ * capacity are never written). Null buffers, components outside {1, 3}, H or W
+ * outside [1, 65535], a quantiser outside 1..255, a misaligned workspace, a
+ * capacity below the bound (or a bound past 2^32): NGP_ERR_ARG before any
+ * device work. */
+int ngp_jpeg_encode(const uint8_t* pixels, uint32_t H, uint32_t W, uint32_t components, const uint16_t* qtable_luma,
+                    const uint16_t* qtable_chroma, int16_t* coef_ws, uint8_t* out, size_t capacity, uint32_t* out_len,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,9 @@ SIGNATURES = {
     "ngp_background_backward": [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_u32,
                                 ctypes.c_uint64, c_vp, c_u32, c_u32, c_u32, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp,
                                 c_vp, c_vp],
+    "ngp_jpeg_scan_capacity": [c_u32, c_u32, c_u32],
+    "ngp_jpeg_workspace_elems": [c_u32, c_u32, c_u32],
+    "ngp_jpeg_encode": [c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp],
 }
 _RESTYPES = {
     "ngp_last_error": ctypes.c_char_p,
@@ -237,6 +240,8 @@ _RESTYPES = {
     "ngp_grad_exchange_words": ctypes.c_uint64,
     "ngp_mesh_workspace_bytes": c_sz,
     "ngp_background_scratch_bytes": c_sz,
+    "ngp_jpeg_scan_capacity": c_sz,
+    "ngp_jpeg_workspace_elems": c_sz,
 }
 
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}

@@ -27,6 +27,11 @@ poses where the scene has no transforms_test.json, and writes
 <workspace>/results/ngp_<i>_rgb.png and _depth.png, as the reference's
 trainer.test does (main_nerf.py:188 / :239); --write_frames does the same at
 the end of a training run. The frames are made on the device (nerf/frames.py).
+--video also writes results/ngp_rgb.avi and ngp_depth.avi, the reference's
+ngp_rgb.mp4 / ngp_depth.mp4 (trainer.test(write_video=True)) as Motion-JPEG:
+every frame is JPEG-encoded on the device (csrc/jpeg.hip, DESIGN.md section
+19); --video_only leaves the PNGs out, --video_fps / --video_quality set the
+rate (25) and the JPEG quality (90).
 --bg_radius R > 0 adds the reference's background model (nerf/network.py
 :107-129): what lies outside the box is learned as a colour per direction on
 the sphere of radius R (a 2-D hash grid and a small MLP), trained against the
@@ -118,6 +123,13 @@ def get_parser():
                    help="steps of the interpolated camera path when the scene has no transforms_test.json")
     p.add_argument("--write_frames", action="store_true",
                    help="after training and evaluation, write the test frames to <workspace>/results")
+    # the test frames as video (the reference's trainer.test(write_video=True): ngp_rgb.mp4 / ngp_depth.mp4)
+    p.add_argument("--video", action="store_true",
+                   help="with --test or --write_frames: also write results/ngp_rgb.avi and ngp_depth.avi, "
+                        "Motion-JPEG encoded on the device")
+    p.add_argument("--video_fps", type=int, default=25, help="frames per second of the videos")
+    p.add_argument("--video_quality", type=int, default=90, help="JPEG quality of the videos' frames, 1..100")
+    p.add_argument("--video_only", action="store_true", help="the videos without the PNG files (implies --video)")
     return p
 
 
@@ -174,7 +186,12 @@ def _write_test_frames(opt, model, train, dev, data_args, source=None, evaluate=
     a split with images: its PSNR and SSIM, printed and added to the result."""
     import torch
 
-    from nerf.frames import FrameRenderer, write_frames
+    from nerf.frames import FrameRenderer, write_frames, write_video
+    video = opt.video or opt.video_only
+    if video and not 1 <= opt.video_quality <= 100:
+        sys.exit(f"[main_nerf] --video_quality must be in 1..100, got {opt.video_quality}")
+    if video and opt.video_fps < 1:
+        sys.exit(f"[main_nerf] --video_fps must be at least 1, got {opt.video_fps}")
     poses, H, W, intrinsics, what, test = _test_path(opt, train, dev, data_args)
     was_training = model.training
     model.eval()
@@ -185,12 +202,20 @@ def _write_test_frames(opt, model, train, dev, data_args, source=None, evaluate=
     out_dir = os.path.join(opt.workspace, "results")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    paths = write_frames(fr, out_dir, "ngp")
+    if video:
+        videos, paths = write_video(fr, out_dir, "ngp", fps=opt.video_fps, quality=opt.video_quality,
+                                    png=not opt.video_only)
+    else:
+        paths = write_frames(fr, out_dir, "ngp")
     secs = time.perf_counter() - t0
     model.train(was_training)
     print(f"[main_nerf] {len(fr)} frames {H}x{W} ({what}) in {secs:.2f} s, {len(fr) / secs:.1f} frames/s, "
           f"written to {out_dir}")
     result = {"frames": len(fr), "frames_per_second": len(fr) / secs, "results": out_dir, "frame_paths": paths}
+    if video:
+        print(f"[main_nerf] videos {videos[0]} and {videos[1]} ({opt.video_fps} frames/s, quality "
+              f"{opt.video_quality})")
+        result["video_paths"] = videos
     if evaluate and (test is None or getattr(test, "images", None) is None):
         print("[main_nerf] --ssim: the test frames have no images to compare with (an interpolated camera path)")
     elif evaluate:

@@ -13,8 +13,11 @@ both to uint8, so 4 bytes per pixel leave the device instead of 16.
 q(x) = uint8(clamp(x, 0, 1) * 255), truncating, 0 for a non-finite x: the
 reference's cast, made total (a ray that misses the box has depth 0 / 0).
 
-No video is written: the reference's imageio.mimwrite needs an encoder this
-project does not depend on; the PNG sequence is the output. DESIGN.md §14."""
+The reference's imageio.mimwrite (<name>_rgb.mp4 / _depth.mp4) needs an
+encoder this project does not depend on; write_video keeps the same frames as
+Motion-JPEG instead, <name>_rgb.avi / _depth.avi, encoded on the device
+(csrc/jpeg.hip, nerf/jpeg.py, nerf/video.py), beside the PNG sequence or in
+its place. DESIGN.md §14, §19."""
 import ctypes
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -166,3 +169,63 @@ def write_frames(renderer, out_dir, name, compress_level=1):
             for f in pair:
                 paths.append(f.result())
     return paths
+
+
+def write_video(renderer, out_dir, name, fps=25, quality=90, png=True):
+    """Render renderer's path once and write {name}_rgb.avi and
+    {name}_depth.avi under out_dir (the reference's {name}_rgb.mp4 / _depth.mp4,
+    utils.py:793-794, as Motion-JPEG in AVI): every frame's rgb8 and depth8 are
+    encoded on the device at `quality` (nerf.jpeg.JpegEncoder, 3 components and
+    1), and frame i's two files are appended while frame i + 1 renders. png:
+    also the PNG sequence, the files write_frames writes for the path; without
+    it the uint8 images never leave the device. -> (the two video paths, the
+    PNG paths in write_frames' order)."""
+    from .jpeg import JpegEncoder
+    from .video import AviWriter
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = renderer.H, renderer.W
+    encoders = (JpegEncoder(H, W, 3, quality, renderer.dev), JpegEncoder(H, W, 1, quality, renderer.dev))
+    videos = [os.path.join(out_dir, f"{name}_{kind}.avi") for kind in ("rgb", "depth")]
+    writers = [AviWriter(p, W, H, fps) for p in videos]
+
+    def rendered():  # frame after frame on the device, and on the host where the PNGs need it
+        if png:
+            yield from renderer.frames()
+        else:
+            for i in range(len(renderer)):
+                renderer.render(i)
+                yield None, None
+
+    paths, pending = [], []
+    try:
+        with ThreadPoolExecutor(max_workers=4) as pool:
+            frames = rendered()
+            i = 0
+            while True:
+                if len(pending) == 2:  # as in write_frames: frame i - 2 holds frame i's pinned pair
+                    for f in pending.pop(0):
+                        paths.append(f.result())
+                try:
+                    rgb, depth = next(frames)
+                except StopIteration:
+                    break
+                for enc, image in zip(encoders, (renderer.rgb8, renderer.depth8)):
+                    enc.submit(image)
+                if i:  # frame i - 1's bytes landed while frame i rendered
+                    for enc, w in zip(encoders, writers):
+                        w.add(enc.result())
+                if png:
+                    stem = os.path.join(out_dir, f"{name}_{i:04d}")
+                    pending.append((pool.submit(_save_png, rgb, stem + "_rgb.png", 1),
+                                    pool.submit(_save_png, depth, stem + "_depth.png", 1)))
+                i += 1
+            if i:
+                for enc, w in zip(encoders, writers):
+                    w.add(enc.result())
+            for pair in pending:
+                for f in pair:
+                    paths.append(f.result())
+    finally:
+        for w in writers:
+            w.close()
+    return videos, paths
