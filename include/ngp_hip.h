@@ -1125,6 +1125,56 @@ int ngp_mesh_emit(const float* volume, uint32_t nx, uint32_t ny, uint32_t nz, fl
                   const void* ws, size_t ws_bytes, uint64_t V, uint64_t T, float* vertices, float* normals,
                   int32_t* faces, void* stream);
 
+/* After the extraction: connected components, cleaning and vertex colours of
+ * an indexed triangle mesh (vertices f32 [V, 3], faces int32 [T, 3], normals
+ * f32 [V, 3]). No reference counterpart: its save_mesh, :688-708, hands the
+ * arrays to trimesh unprocessed. Common to the entries: V or T >= 2^31 is
+ * NGP_ERR_UNSUPPORTED, a null required pointer NGP_ERR_ARG, both before any
+ * device work; a triangle with an index outside [0, V) is never dereferenced,
+ * belongs to no component and is dropped by the clean. Integer atomics only,
+ * with order-independent results, and no kernel waits for another thread. */
+
+/* labels int32 [V]: the smallest vertex index of v's component (two vertices
+ * are connected when a triangle holds both; a vertex no triangle uses is a
+ * component of its own). comp_faces int32 [V]: at a label the number of
+ * triangles of its component, 0 elsewhere. Lock-free union-find in labels,
+ * three launches (init, hook, compress + count); DESIGN.md §20 has the
+ * invariant. V = 0: nothing is launched; T = 0: faces is not read. */
+int ngp_mesh_components(const int32_t* faces, uint64_t V, uint64_t T, int32_t* labels, int32_t* comp_faces,
+                        void* stream);
+/* Cleaning, pass 1, on ngp_mesh_components' labels and comp_faces. A component
+ * is kept when comp_faces >= min_faces and, with keep_largest, it is also the
+ * one with the most triangles (a tie: the smaller label). A triangle is kept
+ * when its indices are valid and its component is kept; a vertex when a kept
+ * triangle uses it (so unreferenced vertices go too). The kept flags and their
+ * exclusive scans go to the workspace (placement by scans, no atomics: the
+ * original order is kept and two runs give the same bytes). counts: device
+ * uint64[4] = V', T', the components before, the components the rule keeps;
+ * the caller reads them once to allocate the outputs of ngp_mesh_clean_emit.
+ * 0 from ngp_mesh_clean_workspace_bytes: V or T >= 2^31. */
+size_t ngp_mesh_clean_workspace_bytes(uint64_t V, uint64_t T);
+int ngp_mesh_clean_count(const int32_t* faces, uint64_t V, uint64_t T, const int32_t* labels,
+                         const int32_t* comp_faces, uint32_t min_faces, int32_t keep_largest, void* ws,
+                         size_t ws_bytes, uint64_t* counts, void* stream);
+/* Pass 2, on the workspace ngp_mesh_clean_count filled from the same mesh:
+ * vertices_out f32 [V2, 3] and normals_out f32 [V2, 3] (nullable, needs
+ * normals) are the kept vertices in their original order, faces_out int32
+ * [T2, 3] the kept triangles in theirs with the indices remapped. V2 = T2 = 0:
+ * nothing is launched. V2 > V or T2 > T: NGP_ERR_ARG. */
+int ngp_mesh_clean_emit(const float* vertices, const float* normals, const int32_t* faces, uint64_t V, uint64_t T,
+                        const void* ws, size_t ws_bytes, uint64_t V2, uint64_t T2, float* vertices_out,
+                        float* normals_out, int32_t* faces_out, void* stream);
+/* The view directions of a vertex colour query, dirs f32 [n, 3] = -normal /
+ * |normal| in fp32: a camera that looks straight at the surface. A normal
+ * whose length is zero or not finite gives (0, 0, 1). */
+int ngp_mesh_color_dirs(const float* normals, uint64_t n, float* dirs, void* stream);
+/* rgb u8 [n, 3] from the first three of each row of `stride` halves: logits
+ * != 0 (ngp_nerf_forward's color_out, stride 16): sigmoid 1 / (1 + expf(-x))
+ * in fp32 first; then ngp_frame_finish's q(x) = (uint8)(clamp(x, 0, 1) *
+ * 255.0f), truncating, 0 for a NaN. Exactly n rows are written. */
+int ngp_mesh_color_finish(const void* values, uint32_t stride, uint64_t n, int32_t logits, uint8_t* rgb,
+                          void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Whole frames around the device-driven render loop (replaces the per-frame */
 /* get_rays + near_far + render_init before it and the blend / quantisation  */

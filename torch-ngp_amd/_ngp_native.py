@@ -202,6 +202,14 @@ SIGNATURES = {
     "ngp_mesh_count": [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_sz, c_vp, c_vp],
     "ngp_mesh_emit": [c_vp, c_u32, c_u32, c_u32, c_f32, c_vp, c_vp, c_sz, ctypes.c_uint64, ctypes.c_uint64,
                       c_vp, c_vp, c_vp, c_vp],
+    "ngp_mesh_components": [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, c_vp],
+    "ngp_mesh_clean_workspace_bytes": [ctypes.c_uint64, ctypes.c_uint64],
+    "ngp_mesh_clean_count": [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, c_u32, c_i32, c_vp, c_sz, c_vp,
+                             c_vp],
+    "ngp_mesh_clean_emit": [c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_sz, ctypes.c_uint64,
+                            ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp],
+    "ngp_mesh_color_dirs": [c_vp, ctypes.c_uint64, c_vp, c_vp],
+    "ngp_mesh_color_finish": [c_vp, c_u32, ctypes.c_uint64, c_i32, c_vp, c_vp],
     "ngp_frame_begin": [c_vp, c_u32, c_u32, c_vp, c_u32, c_u32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "ngp_frame_finish": [c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -239,6 +247,7 @@ _RESTYPES = {
     "ngp_grad_exchange_bins": c_u32,
     "ngp_grad_exchange_words": ctypes.c_uint64,
     "ngp_mesh_workspace_bytes": c_sz,
+    "ngp_mesh_clean_workspace_bytes": c_sz,
     "ngp_background_scratch_bytes": c_sz,
     "ngp_jpeg_scan_capacity": c_sz,
     "ngp_jpeg_workspace_elems": c_sz,

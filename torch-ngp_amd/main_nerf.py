@@ -101,6 +101,12 @@ def get_parser():
     p.add_argument("--save_mesh", action="store_true", help="write <workspace>/meshes/ngp.ply after the evaluation")
     p.add_argument("--mesh_resolution", type=int, default=256, help="lattice points per axis of the mesh's volume")
     p.add_argument("--mesh_threshold", type=float, default=10, help="density at which the surface is drawn")
+    p.add_argument("--mesh_color", action="store_true",
+                   help="colour the mesh's vertices with the model's colour seen along the normal (red green blue)")
+    p.add_argument("--mesh_min_faces", type=int, default=0,
+                   help="drop connected components of the mesh with fewer triangles than this (0: off)")
+    p.add_argument("--mesh_keep_largest", action="store_true",
+                   help="keep only the connected component of the mesh with the most triangles")
     # EMA, validation while training, resuming (the reference's Trainer(ema_decay=0.95, eval_interval=...),
     # main_nerf.py:219, and its load_checkpoint on start, nerf/utils.py:410-432)
     p.add_argument("--ema_decay", type=float, default=None,
@@ -226,6 +232,29 @@ def _write_test_frames(opt, model, train, dev, data_args, source=None, evaluate=
     return result
 
 
+def _mesh_options(opt):
+    """--mesh_color / --mesh_min_faces / --mesh_keep_largest as save_mesh keywords (none set: none passed) and
+    the dict the cleaning fills."""
+    info = {}
+    if not (opt.mesh_color or opt.mesh_min_faces > 0 or opt.mesh_keep_largest):
+        return {}, info
+    return dict(colors=opt.mesh_color, min_faces=opt.mesh_min_faces, keep_largest=opt.mesh_keep_largest,
+                info=info), info
+
+
+def _mesh_report(opt, path, nv, nt, info, result):
+    text = (f"[main_nerf] mesh {path}: {nv} vertices, {nt} triangles "
+            f"(resolution {opt.mesh_resolution}, threshold {opt.mesh_threshold:g})")
+    result.update(mesh=path, mesh_vertices=nv, mesh_triangles=nt)
+    if info:
+        text += (f", {info['components_kept']} of {info['components']} components kept "
+                 f"({info['vertices_dropped']} vertices, {info['faces_dropped']} triangles dropped)")
+        result.update(mesh_components=info["components"], mesh_components_kept=info["components_kept"])
+    if opt.mesh_color:
+        text += ", vertex colours"
+    print(text)
+
+
 def _test(opt, dev, bound, data_args):
     """--test: the model of a checkpoint, its frames and (--save_mesh) its mesh; nothing is trained."""
     import torch
@@ -253,10 +282,9 @@ def _test(opt, dev, bound, data_args):
     result.update(_write_test_frames(opt, model, None, dev, data_args, source, evaluate=opt.ssim))
     if opt.save_mesh:
         path = os.path.join(opt.workspace, "meshes", "ngp.ply")
-        nv, nt = mesh.save_mesh(model, path, resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)
-        print(f"[main_nerf] mesh {path}: {nv} vertices, {nt} triangles "
-              f"(resolution {opt.mesh_resolution}, threshold {opt.mesh_threshold:g})")
-        result.update(mesh=path, mesh_vertices=nv, mesh_triangles=nt)
+        extra, info = _mesh_options(opt)
+        nv, nt = mesh.save_mesh(model, path, resolution=opt.mesh_resolution, threshold=opt.mesh_threshold, **extra)
+        _mesh_report(opt, path, nv, nt, info, result)
     return result
 
 
@@ -476,10 +504,9 @@ def main(argv=None):
         result.update(ssim=mean_ssim, valid_ssim=valid_ssim)
     if opt.save_mesh:
         ft.workspace = opt.workspace
-        path, nv, nt = ft.save_mesh(resolution=opt.mesh_resolution, threshold=opt.mesh_threshold)
-        print(f"[main_nerf] mesh {path}: {nv} vertices, {nt} triangles "
-              f"(resolution {opt.mesh_resolution}, threshold {opt.mesh_threshold:g})")
-        result.update(mesh=path, mesh_vertices=nv, mesh_triangles=nt)
+        extra, info = _mesh_options(opt)
+        path, nv, nt = ft.save_mesh(resolution=opt.mesh_resolution, threshold=opt.mesh_threshold, **extra)
+        _mesh_report(opt, path, nv, nt, info, result)
     if opt.write_frames:
         result.update(_write_test_frames(opt, model, train, dev, data_args, source))
     return result

@@ -1539,18 +1539,25 @@ class FusedTrainer:
             raise RuntimeError("FusedTrainer.ema_params: the trainer was built without ema_decay")
         return [self.ema_shadow[a:a + p.numel()].view(p.shape) for a, p in zip(self._starts, self.params)]
 
-    def save_mesh(self, path=None, resolution=256, threshold=10):
+    def save_mesh(self, path=None, resolution=256, threshold=10, colors=False, min_faces=0, keep_largest=False,
+                  info=None):
         """Trainer.save_mesh (nerf/utils.py:688-708): the pending update is
         applied first, then nerf.mesh.save_mesh writes the density field's mesh
         over aabb_infer as a binary PLY. path None: <workspace>/meshes/ngp.ply
-        when `workspace` is set. -> (path, vertex count, triangle count)."""
+        when `workspace` is set. colors / min_faces / keep_largest / info:
+        nerf.mesh.save_mesh's (small components dropped, vertex colours from
+        the same weights as the density). -> (path, vertex count, triangle
+        count) of what was written."""
         from . import mesh
         if path is None:
             if not self.workspace:
                 raise RuntimeError("FusedTrainer.save_mesh: a path is needed (the trainer has no workspace)")
             path = os.path.join(self.workspace, "meshes", "ngp.ply")
         self.flush()
-        nv, nt = mesh.save_mesh(self.model, path, resolution=resolution, threshold=threshold)
+        extra = {}
+        if colors or min_faces or keep_largest:
+            extra = dict(colors=colors, min_faces=min_faces, keep_largest=keep_largest, info=info)
+        nv, nt = mesh.save_mesh(self.model, path, resolution=resolution, threshold=threshold, **extra)
         return path, nv, nt
 
     def capture(self, warmup=2, ring=0, multi=1):
