@@ -1364,6 +1364,59 @@ int ngp_jpeg_encode(const uint8_t* pixels, uint32_t H, uint32_t W, uint32_t comp
                     const uint16_t* qtable_chroma, int16_t* coef_ws, uint8_t* out, size_t capacity, uint32_t* out_len,
                     void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Signed distance fields of triangle meshes: csrc/sdf.hip, DESIGN.md 21      */
+/* ------------------------------------------------------------------------ */
+
+#define NGP_SDF_BLOCK_FACES 64 /* faces per block of the prepared mesh (one box each) */
+#define NGP_SDF_MAPE_BLOCKS 256 /* doubles of the loss's partial sums */
+
+/* The prepared mesh (sdf/provider.py prepare_mesh): T >= 1 faces sorted by the
+ * Morton code of their centroid,
+ *   tris       f32 [T, 9]     the corners a, b, c;
+ *   normals    f32 [T, 7, 3]  per feature code 0..6: the unit face normal, the
+ *                             pseudo-normals of the edges ab, bc, ca (the sum
+ *                             of the two incident face normals) and of the
+ *                             vertices a, b, c (angle weighted), outwards;
+ *   block_aabb f32 [ceil(T / 64), 6]  min then max of every block of 64 faces;
+ *   cdf        f32 [T]        cumulative area fractions, the last one 1. */
+
+/* One training batch of the reference's sdf/provider.py:66-75, points f32
+ * [N, 3]: [0, N/2) on the surface, [N/2, 7N/8) on the surface plus 0.01 *
+ * normal noise, [7N/8, N) uniform in [-1, 1)^3. Point n of step s draws
+ * rng_unit(seed, s, n, stream) of the counter RNG: streams 0 1 2 the triangle
+ * (the first whose cdf entry exceeds u0, at most T - 1) and the barycentrics
+ * (1 - sqrt(u1), sqrt(u1) (1 - u2), sqrt(u1) u2), 3..6 the Box-Muller pairs
+ * (x and y from one, z from the other); a uniform point is 2 u - 1 of streams
+ * 0 1 2. s is counter[0] (device uint32[2]; [1] is the launch's own ticket and
+ * is left 0); the launch leaves counter[0] = s + 1, so no step needs a host
+ * value. tri (nullable) int32 [N]: the source triangle, -1 for a uniform
+ * point. N % 8 != 0: NGP_ERR_ARG before any launch; N == 0: NGP_OK. */
+int ngp_sdf_sample(const float* tris, const float* cdf, uint32_t T, uint32_t N, uint32_t seed, uint32_t* counter,
+                   float* points, int32_t* tri, void* stream);
+
+/* Exact signed distance of n points f32 [n, 3] to the prepared mesh, negative
+ * inside (the reference's -sdf_fn(points)): the minimum over all faces of the
+ * point-to-triangle distance, signed by (p - q) . n_feature of the closest
+ * feature; ties keep the face met first. tri (nullable) int32 [n]: a face in
+ * [0, T) whose distance starts the point's search (anything else: no start).
+ * feature (nullable) int32 [n]: face * 8 + code. cull != 0 skips a block of
+ * faces whose box is farther from every point of a wave than the point's best
+ * distance, with a margin over the rounding of both; the results are the plain
+ * scan's bit for bit. n == 0: NGP_OK without a launch. */
+int ngp_sdf_query(const float* points, uint32_t n, const float* tris, const float* normals, const float* block_aabb,
+                  uint32_t T, const int32_t* tri, int32_t cull, float* sdf, int32_t* feature, void* stream);
+
+/* The reference's loss.py mape_loss over n elements: *loss (device double) =
+ * mean(|pred - y| / (|y| + 1e-2)), every term in float64, summed in a fixed
+ * order through partials (device double[NGP_SDF_MAPE_BLOCKS]). grad
+ * (nullable, pred's dtype): sign(pred - y) / ((|y| + 1e-2) n) evaluated as
+ * torch's fp32 backward of that formula does, (1 / n) / (|y| + 0.01f) *
+ * sign, times *grad_scale (device float, nullable) before the rounding to
+ * pred's dtype. pred_dtype NGP_DTYPE_F32 or NGP_DTYPE_F16; n in [1, 2^24). */
+int ngp_sdf_mape(const void* pred, int32_t pred_dtype, const float* y, uint64_t n, const float* grad_scale, void* grad,
+                 double* partials, double* loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

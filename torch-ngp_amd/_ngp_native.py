@@ -225,6 +225,9 @@ SIGNATURES = {
     "ngp_jpeg_scan_capacity": [c_u32, c_u32, c_u32],
     "ngp_jpeg_workspace_elems": [c_u32, c_u32, c_u32],
     "ngp_jpeg_encode": [c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp],
+    "ngp_sdf_sample": [c_vp, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
+    "ngp_sdf_query": [c_vp, c_u32, c_vp, c_vp, c_vp, c_u32, c_vp, c_i32, c_vp, c_vp, c_vp],
+    "ngp_sdf_mape": [c_vp, c_i32, c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {
     "ngp_last_error": ctypes.c_char_p,
