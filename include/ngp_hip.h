@@ -1417,6 +1417,57 @@ int ngp_sdf_query(const float* points, uint32_t n, const float* tris, const floa
 int ngp_sdf_mape(const void* pred, int32_t pred_dtype, const float* y, uint64_t n, const float* grad_scale, void* grad,
                  double* partials, double* loss, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* TensoRF's vector-matrix decomposition: csrc/tensorf.hip, DESIGN.md 22      */
+/* ------------------------------------------------------------------------ */
+
+#define NGP_VM_MAX_RES 4096  /* texels per axis */
+#define NGP_VM_MAX_RANK 1024 /* components per plane / line */
+#define NGP_VM_FIXED_BITS 32 /* the backward's quantum: 2^-32 of the power of two above max |g| */
+
+/* One set of the decomposition: component i is plane[i] f32 [H, W, rank[i]]
+ * times line[i] f32 [D, rank[i]], with W = res[m0], H = res[m1], (m0, m1) =
+ * (0,1) (0,2) (1,2) and D = res[v], v = 2 1 0, for i = 0 1 2. */
+typedef struct ngp_vm_set {
+    const float* plane[3];
+    const float* line[3];
+    uint32_t rank[3];
+} ngp_vm_set;
+
+/* x f32 [N, 3] in world units, aabb6 (device) f32 [6]: c = 2 * (x - lo) / (hi -
+ * lo) - 1 in float32 in that order, then every plane at (c[m0], c[m1]) and
+ * every line at c[v] as grid_sample(mode='bilinear', padding_mode='zeros',
+ * align_corners=True) samples them (a texel outside the texture counts as
+ * zero). sum_set (nullable): sigma_feat f32 [N] = sum_i sum_r plane_i[r] *
+ * line_i[r]. cat_set (nullable): prod f32 [N, sum_i rank_i], the products,
+ * component-major. N == 0: NGP_OK without a launch; N < 2^30. */
+int ngp_vm_forward(const float* x, uint32_t N, const float* aabb6, uint32_t res0, uint32_t res1, uint32_t res2,
+                   const ngp_vm_set* sum_set, float* sigma_feat, const ngp_vm_set* cat_set, float* prod, void* stream);
+
+/* The gradient values of the sets given (nullable each): per set, sum_set
+ * first, the planes 0 1 2 then the lines 0 1 2, each in its parameter's
+ * layout; and the bytes of the backward's scratch for them. 0: bad arguments. */
+size_t ngp_vm_grad_values(uint32_t res0, uint32_t res1, uint32_t res2, const ngp_vm_set* sum_set,
+                          const ngp_vm_set* cat_set);
+size_t ngp_vm_backward_scratch_bytes(uint32_t res0, uint32_t res1, uint32_t res2, const ngp_vm_set* sum_set,
+                                     const ngp_vm_set* cat_set);
+
+/* grads f32 [ngp_vm_grad_values] = the gradients of every plane and line of
+ * the sets given, from grad_sigma_feat f32 [N] and / or grad_prod f32 [N, sum
+ * rank] (nullable each: that set's gradients are zero); the interpolation is
+ * recomputed from x. There is no gradient to x. Every contribution is rounded
+ * to the nearest multiple of the quantum q = 2^(E - NGP_VM_FIXED_BITS), 2^E
+ * the smallest power of two above the largest |g| of both gradients, and
+ * summed in 64-bit integers: the result does not depend on the order of the
+ * additions, and an entry with K contributions is within K q / 2 of the exact
+ * sum of its float32 contributions. A gradient that is not finite, or a
+ * contribution of 2^40 quanta or more (a weight times a parameter of 256 or
+ * more times the largest g), makes every value of grads NaN. scratch: the
+ * launcher clears it. N <= 2^22. */
+int ngp_vm_backward(const float* x, uint32_t N, const float* aabb6, uint32_t res0, uint32_t res1, uint32_t res2,
+                    const ngp_vm_set* sum_set, const float* grad_sigma_feat, const ngp_vm_set* cat_set,
+                    const float* grad_prod, void* scratch, size_t scratch_bytes, float* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,10 @@ SIGNATURES = {
     "ngp_sdf_sample": [c_vp, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp],
     "ngp_sdf_query": [c_vp, c_u32, c_vp, c_vp, c_vp, c_u32, c_vp, c_i32, c_vp, c_vp, c_vp],
     "ngp_sdf_mape": [c_vp, c_i32, c_vp, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_vm_forward": [c_vp, c_u32, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "ngp_vm_grad_values": [c_u32, c_u32, c_u32, c_vp, c_vp],
+    "ngp_vm_backward_scratch_bytes": [c_u32, c_u32, c_u32, c_vp, c_vp],
+    "ngp_vm_backward": [c_vp, c_u32, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp],
 }
 _RESTYPES = {
     "ngp_last_error": ctypes.c_char_p,
@@ -254,6 +258,8 @@ _RESTYPES = {
     "ngp_background_scratch_bytes": c_sz,
     "ngp_jpeg_scan_capacity": c_sz,
     "ngp_jpeg_workspace_elems": c_sz,
+    "ngp_vm_grad_values": c_sz,
+    "ngp_vm_backward_scratch_bytes": c_sz,
 }
 
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}
@@ -309,6 +315,14 @@ class DistLossJob(ctypes.Structure):
     its optional per-ray output, of ngp_nerf_composite_loss_dist."""
     _fields_ = [("weight", c_f32), ("loss_dist_ray", c_vp)]
 
+
+class VMSet(ctypes.Structure):
+    """ngp_vm_set (include/ngp_hip.h): three planes [H, W, R] and three lines
+    [D, R] of TensoRF's vector-matrix decomposition, and their ranks."""
+    _fields_ = [("plane", c_vp * 3), ("line", c_vp * 3), ("rank", c_u32 * 3)]
+
+
+VM_FIXED_BITS = 32  # NGP_VM_FIXED_BITS
 
 _lib = None
 
