@@ -1468,6 +1468,60 @@ int ngp_vm_backward(const float* x, uint32_t N, const float* aabb6, uint32_t res
                     const ngp_vm_set* sum_set, const float* grad_sigma_feat, const ngp_vm_set* cat_set,
                     const float* grad_prod, void* scratch, size_t scratch_bytes, float* grads, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* D-NeRF: the time-sliced density grid and the deformation network's input  */
+/* row: csrc/dnerf.hip, DESIGN.md 23                                          */
+/* ------------------------------------------------------------------------ */
+
+/* Grid shape of every entry below: 1 <= T <= 1024 time slices, 1 <= C <= 16
+ * cascades, H a power of two in [2, 1024], T * C * H^3 < 2^32; NGP_ERR_ARG
+ * otherwise, before any device work. grid f32 [T, C, H^3]: a cell's flat index
+ * is (t * C + c) * H^3 + morton3D(cell). */
+
+#define NGP_DNERF_ENCODE_COLS 76 /* 3 + 3 * 2 * 10 columns of x, then 1 + 2 * 6 of t */
+
+/* out [N, NGP_DNERF_ENCODE_COLS] with rows row_stride elements apart (>= the
+ * columns; the elements past a row's columns are not written), out_dtype
+ * NGP_DTYPE_F32 or NGP_DTYPE_F16: the frequency encoding of x f32 [N, 3] with
+ * 10 octaves, then that of the time with 6, in ngp_freq_encode_forward's
+ * column order (the input, then per octave f the sines of 2^f * input, then
+ * the cosines), with accurate sinf / cosf. t f32: one value for every row
+ * (t_stride 0) or one per row (t_stride 1). N == 0: NGP_OK without a launch;
+ * N * 76 < 2^32. */
+int ngp_dnerf_encode(const float* x, const float* t, uint32_t t_stride, uint32_t N, void* out, int32_t out_dtype,
+                     uint32_t row_stride, void* stream);
+
+/* The query points [lo, hi) of update number `update` of the time-sliced
+ * grid: xyzs f32 [hi - lo, 3], times f32 [hi - lo], indices i32 [hi - lo]
+ * (flat cell indices), a pure function of (seed, update, point) through the
+ * counter RNG in a domain of its own (and, for partial updates, of the grid).
+ * Points are numbered slice-major, then cascade. partial == 0: every cell,
+ * point p is cell p (the grid is not read; grid, ws may be null). partial != 0:
+ * per slice and cascade N = H^3 / 4 uniformly drawn cells, then N cells drawn
+ * i.i.d. with replacement from that slice and cascade's occupied cells
+ * (grid > 0), or uniformly where it has none; ws: the occupied lists, of
+ * ngp_dnerf_grid_points_workspace_bytes(T, C, H) bytes (0: bad shape).
+ * Position: (2 c / (H - 1) - 1) * (bound_c - hgs) + (2 u - 1) * hgs, bound_c =
+ * min(2^c, bound), hgs = bound_c / H, with the fp32 operations of
+ * ngp_density_grid_points. Time: (t + 0.5) / T + (2 u - 1) * 0.5 / T, drawn per
+ * point, kept inside [float(t) / float(T), float(t + 1) / float(T)].
+ * hi == lo: NGP_OK without a launch. */
+size_t ngp_dnerf_grid_points_workspace_bytes(uint32_t T, uint32_t C, uint32_t H);
+int ngp_dnerf_grid_points(const float* grid, uint32_t T, uint32_t C, uint32_t H, float bound, uint32_t partial,
+                          uint32_t seed, uint32_t update, uint32_t lo, uint32_t hi, void* ws, size_t ws_bytes,
+                          float* xyzs, float* times, int32_t* indices, void* stream);
+
+/* ngp_density_grid_ema_pack over every slice: where grid >= 0 and tmp_grid >=
+ * 0, grid = max(grid * decay, tmp_grid); tmp_grid reset to -1; stats[0] = the
+ * sum of clamp(grid, 0) over all T * C * H^3 cells in double, added in a fixed
+ * order without atomics (stats: NGP_DNERF_STATS_LEN doubles); bitfield u8 [T,
+ * C * H^3 / 8] at min(mean_density, density_thresh), mean_density =
+ * float(stats[0] / (T * C * H^3)): the mean over the whole grid, not a
+ * slice's. A NaN mean clears every bit. grid 16-byte aligned. Two launches. */
+#define NGP_DNERF_STATS_LEN 1025
+int ngp_dnerf_grid_ema_pack(float* grid, float* tmp_grid, uint32_t T, uint32_t C, uint32_t H, float decay,
+                            double density_thresh, double* stats, uint8_t* bitfield, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

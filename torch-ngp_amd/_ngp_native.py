@@ -232,6 +232,11 @@ SIGNATURES = {
     "ngp_vm_grad_values": [c_u32, c_u32, c_u32, c_vp, c_vp],
     "ngp_vm_backward_scratch_bytes": [c_u32, c_u32, c_u32, c_vp, c_vp],
     "ngp_vm_backward": [c_vp, c_u32, c_vp, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp],
+    "ngp_dnerf_encode": [c_vp, c_vp, c_u32, c_u32, c_vp, c_i32, c_u32, c_vp],
+    "ngp_dnerf_grid_points_workspace_bytes": [c_u32, c_u32, c_u32],
+    "ngp_dnerf_grid_points": [c_vp, c_u32, c_u32, c_u32, c_f32, c_u32, c_u32, c_u32, c_u32, c_u32, c_vp, c_sz,
+                              c_vp, c_vp, c_vp, c_vp],
+    "ngp_dnerf_grid_ema_pack": [c_vp, c_vp, c_u32, c_u32, c_u32, c_f32, ctypes.c_double, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {
     "ngp_last_error": ctypes.c_char_p,
@@ -260,6 +265,7 @@ _RESTYPES = {
     "ngp_jpeg_workspace_elems": c_sz,
     "ngp_vm_grad_values": c_sz,
     "ngp_vm_backward_scratch_bytes": c_sz,
+    "ngp_dnerf_grid_points_workspace_bytes": c_sz,
 }
 
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}
@@ -323,6 +329,8 @@ class VMSet(ctypes.Structure):
 
 
 VM_FIXED_BITS = 32  # NGP_VM_FIXED_BITS
+DNERF_ENCODE_COLS = 76  # NGP_DNERF_ENCODE_COLS
+DNERF_STATS_LEN = 1025  # NGP_DNERF_STATS_LEN
 
 _lib = None
 
