@@ -291,8 +291,11 @@ def sh_encode_jacobian(inputs, degree, eps=1e-4):
     return out
 
 
-def _sh_values(x, y, z, degree, T):
-    c = lambda a: T(a)  # noqa: E731
+def _sh_values(x, y, z, degree, T, const=None):
+    """`const` converts the literals (default: T itself). The float64 kernels
+    multiply by float32-rounded literals, so their reference passes
+    const=lambda a: T(np.float32(a))."""
+    c = const if const is not None else T
     xy, xz, yz, x2, y2, z2 = x * y, x * z, y * z, x * x, y * y, z * z
     x4, y4, z4 = x2 * x2, y2 * y2, z2 * z2
     x6, y6, z6 = x4 * x2, y4 * y2, z4 * z2

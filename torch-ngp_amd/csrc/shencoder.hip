@@ -105,8 +105,8 @@ extern "C" int ngp_sh_encode_backward(const void* grad, const void* inputs, uint
     (void)inputs;
     NGP_REQUIRE(D == 3, NGP_ERR_ARG, "SH encoder only support input dim == 3");
     NGP_REQUIRE(C >= 1 && C <= 8, NGP_ERR_ARG, "SH encoder only supports degree in [1, 8]");
+    if (B == 0) return NGP_OK;  // empty tensors have null pointers
     NGP_REQUIRE(dy_dx && grad_inputs, NGP_ERR_ARG, "sh_encode_backward: dy_dx and grad_inputs are required");
-    if (B == 0) return NGP_OK;
     hipStream_t st = ngp_stream(stream);
     const uint32_t grid = ngp_div_up(B * D, kShBlock);
     switch (dtype) {
